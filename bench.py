@@ -33,16 +33,29 @@ Multi-GPU (one process per GPU, RCCL):
 and relays rank 0's line; under a launcher WORLD_SIZE must equal --gpus, or the
 run fails.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints
+the line; its one extra object, read off the timed launches and one untimed replay of the
+step (the replay also gives the sample count of `value`):
   roofline      dominant kernel (render_persistent_kernel); the contract's figure: algorithmic
                 gather bytes (512 B/sample = 16 levels x 8 corners x half2) over the
                 kernel's mean duration measured with HIP events on its stream,
                 against the HBM peak -- plus what the counters say really binds it
                 (`limiter`) and the measured HBM rate (`hbm_gbs_measured`).
+--full adds what takes runs of its own:
+  single_view_ms  every pose of the timed steps rendered alone, one view per launch.
+and, at one rank with configs 2/3 (--no-extras drops these):
+  api, fast_interp, march_fast_forward, mlp_kernel, configs, server
+                the host-memory API path, the opt-in and ablated kernel forms, the
+                fused-MLP stage kernel alone, other BASELINE configurations, render_server.
   cpu_baseline  the CPU oracle (a port, not the reference binary: the reference
                 is CUDA-only) timed on this host on a bounded sample.
   parity        the metric's image-quality leg: PSNR / max |d| of the HIP frame
                 against the oracle's frame of that sample.
+and, at N > 1 ranks, the check of the gathered frames against unsharded renders (--check).
+
+--dump-outputs DIR writes what the last timed step computed (the frames a caller of the path
+receives) as DIR/<name>.npy, float32: the whole frames when they fit in 64 MB, else the same
+seeded sample of pixels in every run (dump_sample_index).
 """
 from __future__ import annotations
 
@@ -82,6 +95,8 @@ DEFAULT_VIEWS = 16                 # camera views per step (one launch)
 DEFAULT_DEPTH = 1                  # steps in flight at N = 1 (N > 1: 2, so that the gather of one step overlaps the next)
 CONFIG5_REQUESTS, CONFIG5_RES = 64, 800  # BASELINE.json configs[4]
 PMC_FILE = ROOT / "profiles" / "r06" / "pmc_traffic.json"
+DUMP_BYTES = 64_000_000            # --dump-outputs: at most this much in all
+DUMP_SAMPLE_PIXELS, DUMP_SEED = 1 << 21, 20240  # ... else a seeded sample of this many pixels (16 B + 4 B each: 42 MB)
 
 
 def kernel_source_sha16() -> str:
@@ -106,10 +121,16 @@ def parse_args():
                          "(default); 5 = 64 requests of 800x800 per step, replica-parallel")
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: single-view renders, the api / fast_interp / march_fast_forward / "
+                         "mlp_kernel / configs / server / cpu_baseline objects, and (N > 1) the --check of the gathered frames")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step to DIR/<name>.npy (float32; a fixed seeded sample of pixels "
+                         "when the whole frames exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed region and its line (no api / fast_interp / mlp_kernel / cpu_baseline objects): what the "
-                         "rocprofv3 passes of scripts/profile_gpu.sh run, so that every launch they see is the headline kernel's")
+                    help="with --full: the single-view renders but no api / fast_interp / mlp_kernel / configs / server / cpu_baseline "
+                         "objects -- what scripts/profile_gpu.sh runs, so that every launch its traces see is the headline kernel's")
     ap.add_argument("--cpu-sample-div", type=int, default=1,
                     help="CPU baseline renders a (W/div)x(H/div) frame (default: the whole 1920x1080 frame: a few seconds on 128 cores)")
     ap.add_argument("--frames-in-flight", type=int, default=0, help="steps in flight; 0 = default (1 at N = 1, else 2)")
@@ -129,7 +150,8 @@ def parse_args():
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal on a one-GPU box: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--check", action="store_true", default=None,
-                    help="rank 0 also renders the frame unsharded and compares (default: on whenever there is more than one rank)")
+                    help="rank 0 also renders the frame unsharded and compares (default: on with --full whenever there is more than "
+                         "one rank)")
     ap.add_argument("--no-check", dest="check", action="store_false")
     ap.add_argument("--dry-exchange", action="store_true",
                     help="rehearsal of the N > 1 plumbing WITHOUT a GPU: the same launch, step plan (views per rank, shard / replica "
@@ -187,6 +209,29 @@ def step_pose_indices(i, rank, V, V_step, replica, n_poses):
 def step_root(i, world, gather_root):
     """the rank that assembles step i's frames: step % N (every rank is the sink once in N steps) or always rank 0"""
     return i % world if gather_root == "rotate" else 0
+
+
+def dump_sample_index(n_px, bytes_per_px):
+    """--dump-outputs: None (every pixel) when the frames fit in DUMP_BYTES, else the sorted indices of a seeded sample of
+    DUMP_SAMPLE_PIXELS pixels -- the same pixels in every run with the same arguments, whatever the build"""
+    import numpy as np
+    if n_px * bytes_per_px <= DUMP_BYTES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, min(n_px, DUMP_SAMPLE_PIXELS), replace=False))
+
+
+def dump_outputs(dirpath, planes):
+    """planes: name -> device tensor [pixels, channels] over the same pixels -> dirpath/<name>.npy, float32 [pixels(, channels)]"""
+    import numpy as np
+    import torch
+    n_px = next(iter(planes.values())).shape[0]
+    idx = dump_sample_index(n_px, sum(t.shape[1] * 4 for t in planes.values()))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in planes.items():
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(dirpath, f"{name}.npy"), a if a.shape[1] > 1 else a[:, 0])
 
 
 def dry_exchange(args, rank, world):
@@ -269,6 +314,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -451,13 +498,25 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        # before anything renders again: the replays below write into slot 0's buffers
+        last = slots[(args.steps - 1) % depth]
+        if not dist_on:  # row-major float planes, as bound
+            dump_outputs(args.dump_outputs, {"rgba": last.rgba.view(-1, 4), "depth": last.depth.view(-1, 1)})
+        elif rank == step_root(args.steps - 1, world, args.gather_root):  # the sink holds the step's assembled frames
+            if packed:  # (r, g, b, depth) bytes of the reference's 8-bit image, as float32 0..255
+                dump_outputs(args.dump_outputs, {"rgbd8": last.frame.reshape(-1, 1).view(torch.uint8)})
+            else:
+                dump_outputs(args.dump_outputs, {"rgba": last.frame.reshape(-1, 4)})
+
     # sample counts of THIS rank's share, from the launches themselves: every distinct step composition is replayed once,
     # untimed, and the kernel's counters are read (evaluated samples depend -- a little -- on how rays are batched into
     # rounds, which differs between a view rendered alone and in a batch; the composited ones do not), together with
-    # the duration of one step's launch when it has the chip to itself; and one view alone: what a render_frame costs
+    # the duration of one step's launch when it has the chip to itself; with --full also one view alone: what a
+    # render_frame costs
     stream = slots[0].stream
     single_ms, kern_ms = [], []
-    for j in sorted({j for i in range(args.steps) for j in step_poses(i)}):
+    for j in (sorted({j for i in range(args.steps) for j in step_poses(i)}) if args.full else ()):
         ctx.render(cam, poses[j], stream=stream.cuda_stream)
         torch.cuda.synchronize(dev)
         single_ms.append(float(ctx.stats().render_ms))
@@ -513,7 +572,7 @@ def main():
         total_samples, total_evals, total_composited = local_samples, local_evals, local_composited
 
     check = None
-    if (args.check if args.check is not None else dist_on) and dist_on:
+    if (args.check if args.check is not None else args.full) and dist_on:
         # the gathered (+ untiled) frames of a step must equal unsharded single renders of the same poses
         torch.cuda.synchronize(dev)
         step(0)
@@ -561,7 +620,7 @@ def main():
     addr_per_s = float(np.mean(step_evaluated)) * gather_addr_sample / iso_kern_s
     ta_peak = TA_UNITS * TA_ADDR_PER_CLK * clock_hz if clock_hz else None
     in_flight = mean_kern_s * 1e3 / ms_per_step
-    single_view_ms = float(np.mean(single_ms))
+    single_view_ms = float(np.mean(single_ms)) if single_ms else None  # --full
     # PMC passes cannot run inside this process: the counters of the same command are read from the committed
     # summary -- only when it was collected for exactly this launch shape AND these kernel sources
     pmc = None
@@ -590,8 +649,8 @@ def main():
         "evaluated_over_composited": round(total_samples / max(total_composited, 1), 5),
         "ms_per_frame": round(ms_per_step / V_step, 4),
         # one render_frame call of the reference's API = one view per launch, nothing else on the chip
-        "single_view_ms": round(single_view_ms, 4),
-        "frames_per_s_single": round(1e3 / single_view_ms, 2),
+        "single_view_ms": round(single_view_ms, 4) if single_view_ms else None,
+        "frames_per_s_single": round(1e3 / single_view_ms, 2) if single_view_ms else None,
         "higher_is_better": True,
         "scaling": scaling,
         "vs_baseline": None,
@@ -682,7 +741,7 @@ def main():
         out["sharded_frame_equals_unsharded"] = check
     if world == 1:
         out["config"]["samples_per_frame"] = int(mean_samples_launch / V)
-        if not replica and not args.no_extras and not dist_on:
+        if args.full and not replica and not args.no_extras and not dist_on:
             out["api"] = api_bench(nh, torch, dev, desc, cam, poses, W, H)
             out["fast_interp"] = fast_interp_bench(nh, torch, dev, desc, cams_step, [poses[j] for j in step_poses(0)], W, H, V, ms_per_step / V_step)
             out["march_fast_forward"] = march_ff_bench(nh, torch, dev, desc, cams_step, [poses[j] for j in step_poses(0)], W, H, V)
