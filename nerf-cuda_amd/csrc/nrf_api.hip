@@ -236,6 +236,208 @@ void pack_generic_layer(const _Float16* Wm, uint32_t N, uint32_t K, std::vector<
 }
 
 // R/include/nerf-cuda/render_utils.h:68-77
+// The descriptor checks of nrf_load_model that come before the old model is released: what the reference's vocabulary allows
+// (T/.../grid.h:1403-1411, T/src/fully_fused_mlp.cu:700-725, 653-655; spherical_harmonics.h:394-412); anything outside is
+// refused loudly, never emulated on the CPU
+int validate_model(const nrf_model_desc& d, nrf_level_table& lv) {
+  if (d.abi_version != NRF_ABI_VERSION) return fail(NRF_E_INVALID, "abi_version mismatch");
+  const uint32_t F = d.n_features_per_level;
+  if (F != 1 && F != 2 && F != 4 && F != 8) return fail(NRF_E_INVALID, "GridEncoding: n_features_per_level must be 1, 2, 4, or 8.");
+  if (d.interpolation > NRF_INTERP_SMOOTHSTEP) return fail(NRF_E_INVALID, "Invalid interpolation type");
+  if (d.n_neurons != 16 && d.n_neurons != 32 && d.n_neurons != 64 && d.n_neurons != 128)
+    return fail(NRF_E_INVALID, "FullyFusedMLP: n_neurons must be 16, 32, 64 or 128");
+  if (d.density_hidden_layers < 1 || d.rgb_hidden_layers < 1)
+    return fail(NRF_E_INVALID, "FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
+  if (d.density_hidden_layers + d.rgb_hidden_layers + 2 > (uint32_t)GEN_MAX_LAYERS)
+    return fail(NRF_E_UNSUPPORTED, "HIP path: more than 24 layers in the two MLPs together");
+  if (d.density_n_output < 1 || d.density_n_output > 16)  // wider outputs take tcnn's CUTLASS last layer (out of scope)
+    return fail(NRF_E_UNSUPPORTED, "HIP path: density n_output_dims must be 1..16");
+  const uint32_t raw = dir_raw_width(d);
+  if (d.dir_encoding == NRF_DIR_SH && (d.sh_degree < 1 || d.sh_degree > 8))
+    return fail(NRF_E_INVALID, "SphericalHarmonics: degree must be 1..8");
+  if (raw == 0 || next_multiple(raw, 16u) > (uint32_t)GEN_MAX_DIR_W)
+    return fail(NRF_E_UNSUPPORTED, "HIP path: direction encoding must have 1..112 outputs (after padding to 16)");
+  if (d.density_grid_size < 2 || d.density_grid_size >= (1u << 24) || d.cascade < 1)
+    return fail(NRF_E_INVALID, "bad density grid geometry");
+  if (!(d.bound > 0.0f)) return fail(NRF_E_INVALID, "bound must be positive");
+  int rc = compute_level_table(d, lv);
+  if (rc) return rc;
+  uint64_t expect = 0;
+  rc = expected_params(d, lv, expect);
+  if (rc) return rc;
+  if (d.n_params != expect)  // R/include/nerf-cuda/nerf_network.h:425-427
+    return fail(NRF_E_PARAMS, "Can't set params because number of parameters and model size do not match with each other.");
+  const uint64_t Hh = d.density_grid_size;
+  const uint64_t cells = Hh * Hh * Hh * d.cascade;
+  if (d.density_grid && d.n_density_grid != cells)  // R/src/nerf_render.cu:467-469
+    return fail(NRF_E_PARAMS, "Incompatible number of grid cascades.");
+  if (cells >= (1ull << 32)) return fail(NRF_E_UNSUPPORTED, "density grid too large");
+  return NRF_OK;
+}
+
+// What a model descriptor makes of the device side, decided without a device (nrf_debug_plan: tests/test_instance_plan_cpu.py).
+struct ModelPlan {
+  int rc;                    // NRF_OK, or the refusal (fail() has set the message)
+  nrf_level_table lv;
+  LevelParams lp[16];        // the device's level table: index modes, entry offsets, byte constants, quad copies
+  GenModel gen;              // the generic description without its layers (valid unless stage == NET_HOT)
+  uint32_t gen_wave_bytes;   // LDS bytes per wave of its direction + activation rows (0 when stage == NET_HOT)
+  bool generic_grid;         // a level of LV_GENERIC index arithmetic
+  int own;                   // NET_*: the instance that renders the frames when its march tables fit (set_density_grid)
+  int stage;                 // NET_HOT, NET_WIDE or NET_GENERIC: the stage entry points, the per-strip kernel, the fallback
+  uint32_t quad_mask, quad_far;  // DevModel::quad_mask / quad_far
+  uint64_t table_ref_bytes;  // device bytes of the reference-order table
+  uint64_t table_bytes;      // ... and of the quad copies behind it
+};
+
+// budget_mb: bytes of quad copies allowed (MiB); max_quad_steps: unrolled steps (four levels each) that may have them
+ModelPlan plan_model(const nrf_model_desc& d, bool allow_own, uint64_t budget_mb, int max_quad_steps) {
+  ModelPlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.rc = validate_model(d, p.lv);
+  if (p.rc) return p;
+  const nrf_level_table& lv = p.lv;
+  const uint32_t F = d.n_features_per_level, L = d.n_levels, Wn = d.n_neurons;
+  for (uint32_t l = 0; l < L; ++l) {
+    LevelParams& Lv = p.lp[l];
+    Lv.scale = lv.scale[l];
+    Lv.res = lv.resolution[l];
+    Lv.size = lv.offset[l + 1] - lv.offset[l];
+    Lv.hashed = d.grid_type == NRF_GRID_HASH;
+    // replay grid_index's stride loop (grid.h:106-114) in uint32 to classify the level
+    uint32_t stride = 1, mult[3] = {0, 0, 0};  // mult: what grid_index multiplies x, y, z with (0: the term is skipped)
+    int dims = 0;
+    for (; dims < 3 && stride <= Lv.size; ++dims) {
+      mult[dims] = stride;
+      stride *= Lv.res;  // uint32, as in the reference: wraps for res^3 >= 2^32
+    }
+    const bool uses_hash = Lv.hashed && Lv.size < stride;
+    const bool pow2_size = Lv.size >= 2 && (Lv.size & (Lv.size - 1)) == 0;
+    if (uses_hash && pow2_size) Lv.mode = LV_HASH_POW2;
+    else if (!uses_hash && dims == 3 && Lv.res >= 2 && (uint64_t)Lv.res * Lv.res * Lv.res <= Lv.size) Lv.mode = LV_DENSE;
+    else if (!uses_hash && pow2_size && dims >= 1) Lv.mode = LV_ADD_POW2;  // (x + y * mult[1] + z * mult[2]) & (size - 1), see nrf_device.h
+    else Lv.mode = LV_GENERIC;
+    Lv.my_b = mult[1] << 2;  // (the hashed levels' constants replace these below)
+    Lv.mz_b = mult[2] << 2;
+    p.generic_grid = p.generic_grid || Lv.mode == LV_GENERIC;
+  }
+  // The instance: base.json's shape (F = 2 x 16 levels, Linear; 64 neurons, 1 + 2 hidden layers; a 16-wide direction encoding;
+  // ReLU hidden, density output None, rgb output None or Sigmoid, sigma Exponential) is NET_HOT.  Each register-resident
+  // instance relaxes one axis of it; everything else is the generic instance.
+  GenModel& G = p.gen;
+  G.F = F; G.interp = d.interpolation; G.n_levels = L; G.feat_raw = L * F; G.feat_w = next_multiple(G.feat_raw, 16u);
+  G.feat_k = next_multiple(G.feat_w, 32u); G.width = Wn; G.dir_raw = dir_raw_width(d); G.dir_w = next_multiple(G.dir_raw, 16u);
+  G.rgb_in = 16u + G.dir_w;
+  G.n_dens = d.density_hidden_layers + 1; G.n_rgb = d.rgb_hidden_layers + 1;
+  G.act_stride = std::max(G.feat_k, next_multiple(Wn, 32u)) + 8;  // +16 bytes: consecutive rows start 4 banks apart (ds_read_b128 of 16 rows: conflict-free)
+  G.dir_stride = G.dir_w + 8;
+  const uint32_t dir_w = G.dir_w;
+  const bool grid_base = !p.generic_grid && F == 2 && L == 16 && d.interpolation == NRF_INTERP_LINEAR;
+  const bool mlp_base = Wn == 64 && d.density_hidden_layers == 1 && d.rgb_hidden_layers == 2;
+  const bool dir16 = dir_w == 16;
+  const bool relu = d.density_activation == NRF_ACT_RELU && d.rgb_activation == NRF_ACT_RELU;
+  auto native = [](uint32_t a) {  // (nrf_device.h activate_native; Sine keeps the generic instance)
+    return a == NRF_ACT_RELU || a == NRF_ACT_NONE || a == NRF_ACT_EXPONENTIAL || a == NRF_ACT_SIGMOID || a == NRF_ACT_SQUAREPLUS || a == NRF_ACT_SOFTPLUS;
+  };
+  const bool acts_native = native(d.density_activation) && native(d.rgb_activation);
+  const bool outputs_base = d.density_output_activation == NRF_ACT_NONE && d.sigma_activation == NRF_ACT_EXPONENTIAL &&
+                            (d.rgb_output_activation == NRF_ACT_NONE || d.rgb_output_activation == NRF_ACT_SIGMOID);
+  // a Frequency encoding of 32..80 values: NET_WIDE (the first rgb layer in RK_WIDE K steps); SH of degree 5..8: NET_WIDE_SH
+  const bool freq_wide = dir_w > 16 && dir_w <= 16u * (2u * RK_WIDE - 1u) && d.dir_encoding == NRF_DIR_FREQUENCY;
+  const bool sh_wide = dir_w > 16 && dir_w <= 64 && d.dir_encoding == NRF_DIR_SH;
+  const uint32_t extra_layers = (d.density_hidden_layers - 1) + (d.rgb_hidden_layers - 1);
+  int own = NET_GENERIC;
+  if (!outputs_base) own = NET_GENERIC;
+  else if (grid_base && mlp_base && relu && dir16) own = NET_HOT;
+  else if (grid_base && mlp_base && relu && freq_wide) own = NET_WIDE;
+  else if (!allow_own) own = NET_GENERIC;  // (NRF_WIDTH_INSTANCES=0: A/B runs)
+  else if (grid_base && mlp_base && relu && sh_wide) own = NET_WIDE_SH;
+  else if (grid_base && dir16 && relu && Wn != 64 && d.density_hidden_layers == 1 && d.rgb_hidden_layers == 2)
+    own = Wn == 16 ? NET_W16 : (Wn == 32 ? NET_W32 : NET_W128);  // tcnn's other FullyFusedMLP widths
+  else if (grid_base && dir16 && Wn == 64 && acts_native && extra_layers <= (uint32_t)DEPTH_MAX_WW)
+    own = relu ? NET_DEPTH : NET_ACT;  // other numbers of hidden layers (runtime), hidden activations other than ReLU
+  else if (!p.generic_grid && !grid_base && L * F <= 32 && mlp_base && dir16 && relu)
+    own = F == 1 ? NET_GRID1 : (F == 2 ? NET_GRID2 : (F == 4 ? NET_GRID4 : NET_GRID8));  // another grid in front of base.json's MLPs
+  p.own = own;
+  p.stage = own == NET_HOT || own == NET_WIDE ? own : NET_GENERIC;
+  p.gen_wave_bytes = p.stage != NET_HOT ? gen_dir_bytes(G) + gen_act_bytes(G) : 0u;
+  if (p.stage == NET_GENERIC && render_gen_lds_fixed_bytes(p.gen_wave_bytes) > 160 * 1024) {
+    p.rc = fail(NRF_E_UNSUPPORTED, "HIP path: this network shape needs more LDS than a CU has");
+    return p;
+  }
+  // Device copy of the table: the reference's entries level by level; a dense level is followed by
+  // res^2 + res + 1 copies of its first entries so that x + y*res + z*res^2 (at most
+  // size + res^2 + res when a +1 corner sits on the x = 1 / y = 1 / z = 1 face) needs no modulo.
+  uint64_t entries = 0;
+  for (uint32_t l = 0; l < L; ++l) {
+    LevelParams& Lv = p.lp[l];
+    if (Lv.mode == LV_HASH_POW2 || Lv.mode == LV_ADD_POW2)  // aligned to its own (power-of-two) size: `index & mask | offset` (level_gather)
+      entries = (entries + Lv.size - 1) / Lv.size * Lv.size;
+    Lv.offset = (uint32_t)entries;
+    entries += Lv.size;
+    if (Lv.mode == LV_DENSE) entries += (uint64_t)Lv.res * Lv.res + Lv.res + 1;
+  }
+  p.table_ref_bytes = entries * F * 2;
+  if (p.table_ref_bytes >= (1ull << 32)) {  // level_gather addresses the table by 32-bit byte offsets
+    p.rc = fail(NRF_E_UNSUPPORTED, "hash tables of 4 GiB or more are not supported");
+    return p;
+  }
+  // Cell-major quad copies (round 6; nrf_device.h level_gather_quad) behind the reference-order table, for the instances whose
+  // network phase is network_from_lds with an F = 2 x 16 grid (the hot instance, its wide / width / depth forms): per cell
+  // (x, y, z), x, y < res, z <= res, the four entries of the corners (x | x + 1, y | y + 1, z) as grid_index (grid.h:100-117)
+  // names them.  The reference-order table stays: every other kernel (stage entry points, generic instance) reads it.
+  // A step of the fused kernel (levels 4 jl .. 4 jl + 3, one per lane group) takes quads as a whole or not at all (steps that
+  // mix the two forms run both instruction streams: measured no faster, profiles/r06/quad_sweep.txt); steps are granted in order
+  // while their copies fit the budget (nrf_model_desc.gather_copy_budget_mb).  Copies that end beyond the 4 GiB a buffer
+  // resource's byte offset reaches are FAR: addressed in 16-byte units from the table base (level_gather_quad_far).
+  p.table_bytes = p.table_ref_bytes;
+  if (own != NET_GENERIC && net_grid_f(own) == 0) {
+    uint64_t budget = budget_mb << 20;
+    uint64_t end_bytes = (p.table_ref_bytes + 15) & ~15ull;
+    for (int jl = 0; jl < max_quad_steps; ++jl) {
+      uint64_t step_bytes = 0;
+      bool ok = true;
+      for (int g = 0; g < 4; ++g) {
+        const LevelParams& Lv = p.lp[4 * jl + g];
+        ok = ok && (Lv.mode == LV_DENSE || Lv.mode == LV_HASH_POW2) && Lv.res >= 2 && Lv.res < 1024u;  // (res^2 << 4 < 2^24)
+        step_bytes += (uint64_t)Lv.res * Lv.res * ((uint64_t)Lv.res + 1) * 16;
+      }
+      if (!ok || step_bytes > budget || end_bytes + step_bytes >= (1ull << 36)) continue;
+      const bool far = end_bytes + step_bytes >= (1ull << 32);
+      if (far && own == NET_WIDE) continue;  // (NET_WIDE is compiled without the far form: nrf_render.h network_from_lds)
+      budget -= step_bytes;
+      p.quad_mask |= 15u << (4 * jl);
+      if (far) p.quad_far |= 1u << jl;
+      for (int g = 0; g < 4; ++g) {
+        LevelParams& Lv = p.lp[4 * jl + g];
+        const uint32_t res = Lv.res;
+        Lv.q_off_b = far ? (uint32_t)(end_bytes >> 4) : (uint32_t)end_bytes;
+        Lv.q_my_b = far ? res : res << 4;
+        Lv.q_mz_b = far ? res * res : (res * res) << 4;
+        Lv.q_max = res - 1;
+        end_bytes += (uint64_t)res * res * (res + 1) * 16;
+      }
+    }
+    p.table_bytes = end_bytes;
+  }
+  // byte-offset constants of level_gather / level_gather_wide / level_gather_f1: an entry is 2 F bytes (the generic instance's
+  // literal index arithmetic, gen_level, does not read them)
+  const uint32_t sh_b = F == 8 ? 4u : (F == 4 ? 3u : (F == 1 ? 1u : 2u));
+  for (LevelParams& Lv : p.lp) {
+    const bool hashed_pow2 = Lv.mode == LV_HASH_POW2;
+    Lv.off_b = Lv.offset << sh_b;
+    if (hashed_pow2) {
+      Lv.my_b = 2654435761u << sh_b;
+      Lv.mz_b = 805459861u << sh_b;
+    } else {  // the additive multipliers of the stride loop above (dense: res, res^2; LV_ADD_POW2: possibly wrapped / 0)
+      Lv.my_b = (Lv.my_b >> 2) << sh_b;
+      Lv.mz_b = (Lv.mz_b >> 2) << sh_b;
+    }
+    Lv.mask_b = (hashed_pow2 || Lv.mode == LV_ADD_POW2) ? ((Lv.size - 1) << sh_b) : 0xffffffffu;
+  }
+  return p;
+}
+
 void nerf_matrix_to_ngp(const float p[16], float s, float R[9], float org[3]) {
   const int rows[3] = {1, 2, 0};
   for (int r = 0; r < 3; ++r) {
@@ -266,11 +468,9 @@ struct nrf_context {
   void* d_ctab = nullptr;
   void* d_gen = nullptr;
   void* d_wfrag_gen = nullptr;  // wide models: generic-layout fragments for the stage entry points
-  uint32_t model_hot_grid = 0;  // the loaded model's F if it has a register-resident GRID instance (else 0)
-  uint32_t model_hot_width = 0; // the loaded model's width if it has a register-resident width instance (else 0)
-  bool model_wide_sh = false;   // ... or the NET_WIDE_SH form (SH degree 5..8)
-  void* d_wfrag_hot = nullptr;  // 16 / 32 / 128-neuron models of the base.json shape: fragments of their register-resident instance
-  GenModel gen{};  // host copy of the generic instance's description (valid when dm.generic)
+  int own_net = NET_HOT;        // the loaded model's own instance (plan_model): set_density_grid checks for every grid whether it fits
+  void* d_wfrag_hot = nullptr;  // fragments of the model's own register-resident instance when it is not the stage one
+  GenModel gen{};  // host copy of the generic instance's description (valid unless dm.stage == NET_HOT)
   std::vector<float> host_grid;  // the float density grid the march tables were built from
   bool grid_missing = false;     // loaded without a density grid and none generated yet
   bool allow_persistent = true;  // NRF_PERSISTENT=0 keeps the one-workgroup-per-strip render_kernel (A/B runs)
@@ -510,7 +710,7 @@ void view_roi(const float R[9], const float org[3], const float cam[4], const fl
 // nerf_render.cu:441-466, read by kernel_march_rays): occupancy bits, coarse occupancy, the box of occupied cells,
 // the dilated coarse sets of the visibility walk and the cell-boundary table.  Called by nrf_load_model with the
 // snapshot's grid and by nrf_generate_density_grid with the one evaluated from the network.  Needs c->desc, and
-// c->dm.generic / gen_wave_bytes (LDS budget of the tables).
+// c->dm.stage / gen_wave_bytes (LDS budget of the tables) and c->own_net.
 int set_density_grid(nrf_context* c, const float* density_grid, float mean_density) {
   const nrf_model_desc* d = &c->desc;
   const uint64_t Hh = d->density_grid_size;
@@ -661,11 +861,11 @@ int set_density_grid(nrf_context* c, const float* density_grid, float mean_densi
   {
     const uint64_t words = coarse_shift ? (uint64_t)coarse.size() : 0, fl = ctab.size();
     uint64_t budget = (uint64_t)render_lds_table_max_bytes();
-    if (M.generic) {  // whatever the generic instance's rows leave of the CU's 160 KiB
+    if (M.stage == NET_GENERIC) {  // whatever the generic instance's rows leave of the CU's 160 KiB
       const uint64_t used = (uint64_t)render_gen_lds_fixed_bytes(M.gen_wave_bytes);
       budget = used + budget <= 160u * 1024u ? budget : 160u * 1024u - used;
     }
-    if (M.wide) {  // three workgroups per CU: (160 KiB / 3 - fixed part) for the tables
+    if (M.stage == NET_WIDE) {  // three workgroups per CU: (160 KiB / 3 - fixed part) for the tables
       const uint64_t room = 160u * 1024u / 3u - (uint64_t)render_wide_lds_fixed_bytes();
       budget = budget < room ? budget : room;
     }
@@ -677,47 +877,33 @@ int set_density_grid(nrf_context* c, const float* density_grid, float mean_densi
   M.dilated_level_words = dilated_level_words;
   if (!dilated.empty() && dilated.size() * 4 <= (size_t)N_FRAGS * 64 * 16) M.lds_dilated_words = (uint32_t)dilated.size();
   // The persistent form of the render kernel (one workgroup per CU, waves pull strips from work queues) keeps every march
-  // table in LDS for the whole launch: tables that fit beside the blocks of its waves (16 hot, 12 wide, 12 or 8 generic).
+  // table in LDS for the whole launch: tables that fit beside the blocks of its waves.  The model's own instance if they fit
+  // beside its workgroup (a register-resident instance other than the stage one has the persistent form only), else the
+  // stage instance -- the generic one with 12 waves and its weight fragments in LDS, 12 without, 8 with, 8 without: the first
+  // that fits (NRF_GEN_WLDS=0 at nrf_create: never stage the fragments).  Decided again for every grid (nrf_generate_density_grid).
+  M.net = M.stage;
   M.persistent = 0;
   M.persist_waves = 0;
+  M.gen_weights_lds = 0;
   M.n_cus = (uint32_t)c->n_cus;
-  M.hot_width = c->model_hot_width;  // (decided again for every grid: nrf_generate_density_grid calls this too)
-  M.wide_sh = c->model_wide_sh ? 1u : 0u;
-  M.hot_grid = c->model_hot_grid;
-  bool width_instance = false;  // the model's frames come from the register-resident instance of its width (persistent kernel only)
-  if (c->allow_persistent && M.lds_coarse_words > 0 && (M.hot_width || M.wide_sh || M.hot_grid)) {
+  if (c->allow_persistent && M.lds_coarse_words > 0) {
     const size_t tables = 4 * ((size_t)M.lds_coarse_words + M.lds_ctab_floats + dilated.size());
-    const size_t fixed = M.wide_sh ? (size_t)render_persistent_lds_widesh_bytes()
-                         : M.hot_grid ? (size_t)render_persistent_lds_fixed_bytes(0u, 0u, 0u, 16) : (size_t)render_persistent_lds_width_bytes((int)M.hot_width);
-    if (fixed + tables <= 160u * 1024u) {
-      M.persistent = 1;
-      M.persist_waves = (uint32_t)render_persist_waves_for(M.generic, M.wide, M.wide_sh, M.hot_width, M.hot_grid, march_form(M.H, M.cascade, M.bound));
-      M.gen_weights_lds = 0;
-      M.lds_dilated_words = (uint32_t)dilated.size();
-      width_instance = true;
-    }
-  }
-  if (!width_instance) M.hot_width = M.wide_sh = M.hot_grid = 0;  // (the tables do not fit beside its workgroup: the generic instance renders)
-  if (c->allow_persistent && M.lds_coarse_words > 0 && !width_instance) {
-    const size_t tables = 4 * ((size_t)M.lds_coarse_words + M.lds_ctab_floats + dilated.size());
-    // generic instance: 12 waves with the weight fragments in LDS, 12 waves without, 8 with, 8 without -- the first that fits
-    // (NRF_GEN_WLDS=0 at nrf_create: never stage the fragments)
-    const bool allow_wlds = c->allow_gen_wlds;
-    M.gen_weights_lds = 0;
-    // (the wide instance with the generic march -- a grid size or bound that is no power of two -- is compiled for 8 waves:
-    //  launch_render's choice of the march form, nrf_kernels_wide.hip)
-    const int first_waves = render_persist_waves_for(M.generic, M.wide, 0u, 0u, 0u, march_form(M.H, M.cascade, M.bound));
-    for (int waves : {first_waves, M.generic && first_waves != 8 ? 8 : 0}) {  // (only the generic instance has a second workgroup size)
-      if (waves == 0) break;
-      const size_t fixed = (size_t)render_persistent_lds_fixed_bytes(M.generic, M.wide, M.gen_wave_bytes, waves) + tables;
-      for (int wlds : {1, 0}) {
-        if (wlds && (!M.generic || !allow_wlds)) continue;
-        if (fixed + (wlds ? 16u + M.gen_frag_bytes : 0u) <= 160u * 1024u) {
-          M.persistent = 1;
-          M.persist_waves = (uint32_t)waves;
-          M.gen_weights_lds = (uint32_t)wlds;
-          M.lds_dilated_words = (uint32_t)dilated.size();
-          break;
+    const int form = march_form(M.H, M.cascade, M.bound);
+    for (const int net : {c->own_net, (int)M.stage}) {
+      const int first_waves = render_persist_waves(net, form);
+      for (int waves : {first_waves, net == NET_GENERIC && first_waves != 8 ? 8 : 0}) {  // (only the generic instance has a second size)
+        if (waves == 0 || M.persistent) break;
+        const size_t fixed = (size_t)render_persistent_lds_bytes(net, waves, M.gen_wave_bytes) + tables;
+        for (int wlds : {1, 0}) {
+          if (wlds && (net != NET_GENERIC || !c->allow_gen_wlds)) continue;
+          if (fixed + (wlds ? 16u + M.gen_frag_bytes : 0u) <= 160u * 1024u) {
+            M.net = (uint32_t)net;
+            M.persistent = 1;
+            M.persist_waves = (uint32_t)waves;
+            M.gen_weights_lds = (uint32_t)wlds;
+            M.lds_dilated_words = (uint32_t)dilated.size();
+            break;
+          }
         }
       }
       if (M.persistent) break;
@@ -873,49 +1059,30 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   if (d->abi_version != NRF_ABI_VERSION) return fail(NRF_E_INVALID, "abi_version mismatch");
   int rc = set_device(c);
   if (rc) return rc;
-  // what the reference's vocabulary allows (T/.../grid.h:1403-1411, T/src/fully_fused_mlp.cu:700-725, 653-655;
-  // spherical_harmonics.h:394-412); anything outside is refused loudly, never emulated on the CPU
-  const uint32_t F = d->n_features_per_level;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return fail(NRF_E_INVALID, "GridEncoding: n_features_per_level must be 1, 2, 4, or 8.");
-  if (d->interpolation > NRF_INTERP_SMOOTHSTEP) return fail(NRF_E_INVALID, "Invalid interpolation type");
-  if (d->n_neurons != 16 && d->n_neurons != 32 && d->n_neurons != 64 && d->n_neurons != 128)
-    return fail(NRF_E_INVALID, "FullyFusedMLP: n_neurons must be 16, 32, 64 or 128");
-  if (d->density_hidden_layers < 1 || d->rgb_hidden_layers < 1)
-    return fail(NRF_E_INVALID, "FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
-  if (d->density_hidden_layers + d->rgb_hidden_layers + 2 > (uint32_t)GEN_MAX_LAYERS)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: more than 24 layers in the two MLPs together");
-  if (d->density_n_output < 1 || d->density_n_output > 16)  // wider outputs take tcnn's CUTLASS last layer (out of scope)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: density n_output_dims must be 1..16");
-  const uint32_t raw = dir_raw_width(*d);
-  if (d->dir_encoding == NRF_DIR_SH && (d->sh_degree < 1 || d->sh_degree > 8))
-    return fail(NRF_E_INVALID, "SphericalHarmonics: degree must be 1..8");
-  if (raw == 0 || next_multiple(raw, 16u) > (uint32_t)GEN_MAX_DIR_W)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: direction encoding must have 1..112 outputs (after padding to 16)");
-  if (d->density_grid_size < 2 || d->density_grid_size >= (1u << 24) || d->cascade < 1)
-    return fail(NRF_E_INVALID, "bad density grid geometry");
-  if (!(d->bound > 0.0f)) return fail(NRF_E_INVALID, "bound must be positive");
-
-  nrf_level_table lv;
-  rc = compute_level_table(*d, lv);
-  if (rc) return rc;
-  uint64_t expect = 0;
-  rc = expected_params(*d, lv, expect);
-  if (rc) return rc;
-  if (d->n_params != expect)  // R/include/nerf-cuda/nerf_network.h:425-427
-    return fail(NRF_E_PARAMS, "Can't set params because number of parameters and model size do not match with each other.");
-  const uint64_t Hh = d->density_grid_size;
-  const uint64_t cells = Hh * Hh * Hh * d->cascade;
-  if (d->density_grid && d->n_density_grid != cells)  // R/src/nerf_render.cu:467-469
-    return fail(NRF_E_PARAMS, "Incompatible number of grid cascades.");
-  if (cells >= (1ull << 32)) return fail(NRF_E_UNSUPPORTED, "density grid too large");
-
+  {
+    nrf_level_table lv;
+    rc = validate_model(*d, lv);
+    if (rc) return rc;
+  }
   HIP_TRY(hipDeviceSynchronize());  // nothing may still be reading the old model
   free_model(c);
+  // the budget of the quad copies: a sixteenth of the device's memory (MI355X: 18 GB), and no more than half of what is free --
+  // QUAD_BUDGET_MB_DEFAULT when the device does not say; nrf_model_desc.gather_copy_budget_mb and NRF_QUAD_BUDGET_MB override it
+  uint64_t budget_mb = QUAD_BUDGET_MB_DEFAULT;
+  {
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget_mb = std::min<uint64_t>((uint64_t)mem_total >> 24, (uint64_t)mem_free >> 21);
+    else (void)hipGetLastError();
+  }
+  if (d->gather_copy_budget_mb) budget_mb = d->gather_copy_budget_mb;
+  if (c->quad_budget_mb >= 0) budget_mb = (uint64_t)c->quad_budget_mb;
+  const ModelPlan p = plan_model(*d, c->allow_width_instances, budget_mb, c->quad_levels < 0 ? 4 : std::min(c->quad_levels, 16) / 4);
+  if (p.rc) return p.rc;
+  const nrf_level_table& lv = p.lv;
   // fp32 -> fp16 cast of every parameter (nerf_network.h:434-436), order: density MLP | rgb MLP | grid;
   // each MLP: first [W x in] | hidden [W x W] ... | last [16 x W] (fully_fused_mlp.cu:636-687)
-  const uint32_t L = d->n_levels, Wn = d->n_neurons;
-  const uint32_t feat_raw = L * F, feat_w = next_multiple(feat_raw, 16u);
-  const uint32_t dir_w = next_multiple(raw, 16u), rgb_in = 16u + dir_w;
+  const uint32_t F = d->n_features_per_level, L = d->n_levels, Wn = d->n_neurons;
+  const uint32_t feat_w = p.gen.feat_w, dir_w = p.gen.dir_w, rgb_in = p.gen.rgb_in;
   struct LayerDim { uint32_t N, K, act; };
   std::vector<LayerDim> layers;
   auto add_mlp = [&](uint32_t in, uint32_t hidden, uint32_t act, uint32_t out_act) {
@@ -929,104 +1096,26 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   for (const LayerDim& ly : layers) n_mlp += (size_t)ly.N * ly.K;
   std::vector<_Float16> w16(n_mlp);
   for (size_t i = 0; i < n_mlp; ++i) w16[i] = (_Float16)d->params[i];
-  const size_t n_grid = (size_t)lv.offset[L] * F;
   const float* gp = d->params + n_mlp;
-  std::vector<LevelParams> lp(16);
-  bool generic_grid = false;
-  for (uint32_t l = 0; l < 16; ++l) std::memset(&lp[l], 0, sizeof(LevelParams));
-  for (uint32_t l = 0; l < L; ++l) {
-    LevelParams& Lv = lp[l];
-    Lv.scale = lv.scale[l];
-    Lv.res = lv.resolution[l];
-    Lv.size = lv.offset[l + 1] - lv.offset[l];
-    Lv.hashed = d->grid_type == NRF_GRID_HASH;
-    // replay grid_index's stride loop (grid.h:106-114) in uint32 to classify the level
-    uint32_t stride = 1, mult[3] = {0, 0, 0};  // mult: what grid_index multiplies x, y, z with (0: the term is skipped)
-    int dims = 0;
-    for (; dims < 3 && stride <= Lv.size; ++dims) {
-      mult[dims] = stride;
-      stride *= Lv.res;  // uint32, as in the reference: wraps for res^3 >= 2^32
-    }
-    const bool uses_hash = Lv.hashed && Lv.size < stride;
-    const bool pow2_size = Lv.size >= 2 && (Lv.size & (Lv.size - 1)) == 0;
-    if (uses_hash && pow2_size) Lv.mode = LV_HASH_POW2;
-    else if (!uses_hash && dims == 3 && Lv.res >= 2 && (uint64_t)Lv.res * Lv.res * Lv.res <= Lv.size) Lv.mode = LV_DENSE;
-    else if (!uses_hash && pow2_size && dims >= 1) Lv.mode = LV_ADD_POW2;  // (x + y * mult[1] + z * mult[2]) & (size - 1), see nrf_device.h
-    else Lv.mode = LV_GENERIC;
-    Lv.my_b = mult[1] << 2;  // (the hashed levels' constants replace these below)
-    Lv.mz_b = mult[2] << 2;
-    generic_grid = generic_grid || Lv.mode == LV_GENERIC;
-  }
-  // The register-resident instance is the shape of the reference's base.json; everything else is the generic one.
-  // (a Frequency direction encoding of 32..80 values keeps the register-resident instance: its `wide` form)
-  const bool wide = dir_w > 16 && dir_w <= 16u * (2u * RK_WIDE - 1u) && d->dir_encoding == NRF_DIR_FREQUENCY;
-  const bool generic = generic_grid || F != 2 || L != 16 || Wn != 64 || d->density_hidden_layers != 1 || d->rgb_hidden_layers != 2 ||
-                       !(dir_w == 16 || wide) || d->interpolation != NRF_INTERP_LINEAR ||
-                       !(d->density_activation == NRF_ACT_RELU && d->rgb_activation == NRF_ACT_RELU &&
-                         d->density_output_activation == NRF_ACT_NONE &&
-                         (d->rgb_output_activation == NRF_ACT_NONE || d->rgb_output_activation == NRF_ACT_SIGMOID) &&
-                         d->sigma_activation == NRF_ACT_EXPONENTIAL);
-  // ... except for its width: 16 / 32 / 128 neurons (tcnn's other FullyFusedMLP widths) keep the register-resident form in
-  // the persistent kernel (NET_W16 / NET_W32 / NET_W128); everywhere else such a model is a generic one
-  const bool base_shape_but_width = !generic_grid && F == 2 && L == 16 && d->density_hidden_layers == 1 && d->rgb_hidden_layers == 2 && dir_w == 16 &&
-                                    d->interpolation == NRF_INTERP_LINEAR && d->density_activation == NRF_ACT_RELU && d->rgb_activation == NRF_ACT_RELU &&
-                                    d->density_output_activation == NRF_ACT_NONE &&
-                                    (d->rgb_output_activation == NRF_ACT_NONE || d->rgb_output_activation == NRF_ACT_SIGMOID) &&
-                                    d->sigma_activation == NRF_ACT_EXPONENTIAL;
-  // ... and for its depth: 64 neurons with other numbers of hidden layers (>= 1 each, at most DEPTH_MAX_WW 64 -> 64 layers in all)
-  // keep the register-resident form as the DEPTH instance -- reported as hot_width 64
-  // ... and (round 6) for its hidden activations: any activation of tcnn's vocabulary in either MLP keeps the register-resident form in
-  // the same instance (the activation works on the fp32 accumulators, mlp_tiles_depth) -- base.json's own 1 + 2 layers included
-  const bool relu_both = d->density_activation == NRF_ACT_RELU && d->rgb_activation == NRF_ACT_RELU;
-  auto native_act = [](uint32_t a) {  // (nrf_device.h activate_native; Sine keeps the generic instance)
-    return a == NRF_ACT_RELU || a == NRF_ACT_NONE || a == NRF_ACT_EXPONENTIAL || a == NRF_ACT_SIGMOID || a == NRF_ACT_SQUAREPLUS || a == NRF_ACT_SOFTPLUS;
-  };
-  const bool base_shape_but_depth = native_act(d->density_activation) && native_act(d->rgb_activation) && !generic_grid && F == 2 && L == 16 && Wn == 64 && dir_w == 16 && d->interpolation == NRF_INTERP_LINEAR &&
-                                    d->density_output_activation == NRF_ACT_NONE &&
-                                    (d->rgb_output_activation == NRF_ACT_NONE || d->rgb_output_activation == NRF_ACT_SIGMOID) &&
-                                    d->sigma_activation == NRF_ACT_EXPONENTIAL && d->density_hidden_layers >= 1 && d->rgb_hidden_layers >= 1 &&
-                                    !(d->density_hidden_layers == 1 && d->rgb_hidden_layers == 2 && relu_both) &&
-                                    (d->density_hidden_layers - 1) + (d->rgb_hidden_layers - 1) <= (uint32_t)DEPTH_MAX_WW;
-  const bool hot_depth = base_shape_but_depth && c->allow_width_instances;
-  const uint32_t hot_width = hot_depth ? (relu_both ? 64u : HOT_WIDTH_ACT) : ((base_shape_but_width && (Wn == 16 || Wn == 32 || Wn == 128) && c->allow_width_instances) ? Wn : 0u);
-  // ... and for its direction encoding: SphericalHarmonics of degree 5..8 (32..64 padded values) keeps the register-resident
-  // MLPs in the persistent kernel's NET_WIDE_SH form (per-ray rows of coefficients in LDS)
-  const bool wide_sh = !generic_grid && F == 2 && L == 16 && Wn == 64 && d->density_hidden_layers == 1 && d->rgb_hidden_layers == 2 &&
-                       d->dir_encoding == NRF_DIR_SH && dir_w > 16 && dir_w <= 64 && d->interpolation == NRF_INTERP_LINEAR &&
-                       d->density_activation == NRF_ACT_RELU && d->rgb_activation == NRF_ACT_RELU && d->density_output_activation == NRF_ACT_NONE &&
-                       (d->rgb_output_activation == NRF_ACT_NONE || d->rgb_output_activation == NRF_ACT_SIGMOID) &&
-                       d->sigma_activation == NRF_ACT_EXPONENTIAL && c->allow_width_instances;
-  // ... and for its grid: F = 2 with fewer than 16 levels, F = 4 / 8 with at most 32 features in all, Linear, Smoothstep or -- any F = 2 /
-  // 4 / 8 grid of at most 32 features, the 16 x 2 one included -- Nearest (round 5: one gather per level, grid.h:215-232), every
-  // level dense / power-of-two hashed / LV_ADD_POW2 -- the GRID instances (NET_GRID2 / 4 / 8) keep base.json's MLPs in registers
-  const bool hot_grid_ok = !generic_grid && (F == 1 || F == 2 || F == 4 || F == 8) && !(F == 2 && L == 16 && d->interpolation == NRF_INTERP_LINEAR) && L * F <= 32 &&
-                           Wn == 64 && d->density_hidden_layers == 1 && d->rgb_hidden_layers == 2 && dir_w == 16 &&
-                           (d->interpolation == NRF_INTERP_LINEAR || d->interpolation == NRF_INTERP_SMOOTHSTEP || d->interpolation == NRF_INTERP_NEAREST) &&
-                           d->density_activation == NRF_ACT_RELU && d->rgb_activation == NRF_ACT_RELU && d->density_output_activation == NRF_ACT_NONE &&
-                           (d->rgb_output_activation == NRF_ACT_NONE || d->rgb_output_activation == NRF_ACT_SIGMOID) &&
-                           d->sigma_activation == NRF_ACT_EXPONENTIAL && c->allow_width_instances;
-  const uint32_t hot_grid = hot_grid_ok ? F : 0u;
   std::vector<_Float16> frags, frags_gen, frags_hot;
-  GenModel G;
-  std::memset(&G, 0, sizeof(G));
-  if (!generic) pack_fragments(w16, rgb_in, frags);
-  if (hot_depth) pack_fragments_depth(w16, (int)d->density_hidden_layers, (int)d->rgb_hidden_layers, frags_hot);
-  else if (hot_width) pack_fragments_width(w16, (int)hot_width, frags_hot);
-  if (wide_sh) pack_fragments(w16, rgb_in, frags_hot);  // the wide layout: first rgb layer in RK_WIDE K steps
-  if (hot_grid) pack_fragments_grid(w16, feat_w, rgb_in, F, frags_hot);
+  if (p.stage != NET_GENERIC) pack_fragments(w16, rgb_in, frags);
+  switch (p.own) {  // the fragments of a register-resident instance other than the stage one
+    case NET_W16: case NET_W32: case NET_W128: pack_fragments_width(w16, net_width(p.own), frags_hot); break;
+    case NET_DEPTH: case NET_ACT: pack_fragments_depth(w16, (int)d->density_hidden_layers, (int)d->rgb_hidden_layers, frags_hot); break;
+    case NET_WIDE_SH: pack_fragments(w16, rgb_in, frags_hot); break;  // the wide layout: first rgb layer in RK_WIDE K steps
+    case NET_GRID1: case NET_GRID2: case NET_GRID4: case NET_GRID8: pack_fragments_grid(w16, feat_w, rgb_in, F, frags_hot); break;
+    default: break;
+  }
   // the generic description + fragments: the generic instance's model, and -- for a wide model -- what the stage
   // entry points nrf_encode_dir / nrf_mlp_forward run on (rows of the padded widths)
-  if (generic || wide) {
-    std::vector<_Float16>& fr = generic ? frags : frags_gen;
-    G.F = F; G.interp = d->interpolation; G.n_levels = L; G.feat_raw = feat_raw; G.feat_w = feat_w;
+  GenModel G;
+  std::memset(&G, 0, sizeof(G));
+  if (p.stage != NET_HOT) {
+    std::vector<_Float16>& fr = p.stage == NET_GENERIC ? frags : frags_gen;
+    G = p.gen;
     // 1: F = 2 (level_gather); 4 / 8: that F (level_gather_wide); 0: gen_level's literal index arithmetic (F = 1, Nearest, odd sizes)
-    G.fast_grid = (!generic_grid && (F == 2 || F == 4 || F == 8) && (d->interpolation == NRF_INTERP_LINEAR || d->interpolation == NRF_INTERP_SMOOTHSTEP) &&
+    G.fast_grid = (!p.generic_grid && (F == 2 || F == 4 || F == 8) && (d->interpolation == NRF_INTERP_LINEAR || d->interpolation == NRF_INTERP_SMOOTHSTEP) &&
                    c->allow_gen_fast_grid) ? (F == 2 ? 1u : F) : 0u;
-    G.feat_k = next_multiple(feat_w, 32u); G.width = Wn; G.dir_raw = raw; G.dir_w = dir_w; G.rgb_in = rgb_in;
-    G.n_dens = d->density_hidden_layers + 1; G.n_rgb = d->rgb_hidden_layers + 1;
-    const uint32_t max_k = G.feat_k > next_multiple(Wn, 32u) ? G.feat_k : next_multiple(Wn, 32u);
-    G.act_stride = max_k + 8;   // +16 bytes: consecutive rows start 4 banks apart (ds_read_b128 of 16 rows: conflict-free)
-    G.dir_stride = dir_w + 8;
     const _Float16* wp = w16.data();
     for (size_t i = 0; i < layers.size(); ++i) {
       G.layer[i].frag_off = (uint32_t)(fr.size() / (64 * 8));
@@ -1037,77 +1126,14 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
       wp += (size_t)layers[i].N * layers[i].K;
     }
   }
-  const uint32_t gen_wave_bytes = (generic || wide) ? gen_dir_bytes(G) + gen_act_bytes(G) : 0u;
-  if (generic && render_gen_lds_fixed_bytes(gen_wave_bytes) > 160 * 1024)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: this network shape needs more LDS than a CU has");
-  // Device copy of the table: the reference's entries level by level; a dense level is followed by
-  // res^2 + res + 1 copies of its first entries so that x + y*res + z*res^2 (at most
-  // size + res^2 + res when a +1 corner sits on the x = 1 / y = 1 / z = 1 face) needs no modulo.
-  std::vector<_Float16> grid16;  // F halves per entry
-  grid16.reserve(n_grid + (size_t)F * (16 * 4096 + ((size_t)1 << d->log2_hashmap_size)));
+  // the table at the plan's level offsets (padding zero)
+  std::vector<_Float16> grid16(p.table_ref_bytes / 2, (_Float16)0.0f);
   for (uint32_t l = 0; l < L; ++l) {
-    LevelParams& Lv = lp[l];
-    if (Lv.mode == LV_HASH_POW2 || Lv.mode == LV_ADD_POW2)  // aligned to its own (power-of-two) size: `index & mask | offset` (level_gather)
-      while ((grid16.size() / F) % Lv.size != 0) grid16.push_back((_Float16)0.0f);
-    Lv.offset = (uint32_t)(grid16.size() / F);
+    const LevelParams& Lv = p.lp[l];
     const float* src = gp + (size_t)lv.offset[l] * F;
-    for (size_t i = 0; i < (size_t)Lv.size * F; ++i) grid16.push_back((_Float16)src[i]);
-    if (Lv.mode == LV_DENSE) {
-      const size_t extra = (size_t)Lv.res * Lv.res + Lv.res + 1;
-      for (size_t i = 0; i < extra * F; ++i) grid16.push_back((_Float16)src[i % ((size_t)Lv.size * F)]);
-    }
-  }
-  if ((uint64_t)grid16.size() * 2 >= (1ull << 32))  // level_gather addresses the table by 32-bit byte offsets
-    return fail(NRF_E_UNSUPPORTED, "hash tables of 4 GiB or more are not supported");
-  // Cell-major quad copies (round 6; nrf_device.h level_gather_quad) behind the reference-order table, for the instances whose
-  // network phase is network_from_lds with an F = 2 x 16 grid (the hot instance, its wide / width / depth forms): per cell
-  // (x, y, z), x, y < res, z <= res, the four entries of the corners (x | x + 1, y | y + 1, z) as grid_index (grid.h:100-117)
-  // names them.  The reference-order table stays: every other kernel (stage entry points, generic instance) reads it.
-  // A step of the fused kernel (levels 4 jl .. 4 jl + 3, one per lane group) takes quads as a whole or not at all (steps that
-  // mix the two forms run both instruction streams: measured no faster, profiles/r06/quad_sweep.txt); steps are granted in order
-  // while their copies fit the budget (nrf_model_desc.gather_copy_budget_mb).  Copies that end beyond the 4 GiB a buffer
-  // resource's byte offset reaches are FAR: addressed in 16-byte units from the table base (level_gather_quad_far).
-  uint32_t quad_mask = 0, quad_far = 0;
-  uint64_t table_bytes = (uint64_t)grid16.size() * 2;  // device bytes: the reference-order table + the quad copies (built on the device, below)
-  const bool quad_shape = !generic_grid && F == 2 && L == 16 && d->interpolation == NRF_INTERP_LINEAR && !hot_grid &&
-                          (!generic || hot_width || wide_sh);
-  if (quad_shape) {
-    uint64_t budget_mb = QUAD_BUDGET_MB_DEFAULT;  // (when the device does not say how much memory it has)
-    {
-      size_t mem_free = 0, mem_total = 0;  // default: a sixteenth of the device's memory (MI355X: 18 GB), and no more than half of what is free
-      if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) budget_mb = std::min<uint64_t>((uint64_t)mem_total >> 24, (uint64_t)mem_free >> 21);
-      else (void)hipGetLastError();
-    }
-    if (d->gather_copy_budget_mb) budget_mb = d->gather_copy_budget_mb;
-    if (c->quad_budget_mb >= 0) budget_mb = (uint64_t)c->quad_budget_mb;
-    uint64_t budget = budget_mb << 20;
-    const int max_steps = c->quad_levels < 0 ? 4 : std::min(c->quad_levels, 16) / 4;
-    uint64_t end_bytes = ((uint64_t)grid16.size() * 2 + 15) & ~15ull;
-    for (int jl = 0; jl < max_steps; ++jl) {
-      uint64_t step_bytes = 0;
-      bool ok = true;
-      for (int g = 0; g < 4; ++g) {
-        const LevelParams& Lv = lp[4 * jl + g];
-        ok = ok && (Lv.mode == LV_DENSE || Lv.mode == LV_HASH_POW2) && Lv.res >= 2 && Lv.res < 1024u;  // (res^2 << 4 < 2^24)
-        step_bytes += (uint64_t)Lv.res * Lv.res * ((uint64_t)Lv.res + 1) * 16;
-      }
-      if (!ok || step_bytes > budget || end_bytes + step_bytes >= (1ull << 36)) continue;
-      const bool far = end_bytes + step_bytes >= (1ull << 32);
-      if (far && !generic && wide) continue;  // (NET_WIDE is compiled without the far form: nrf_render.h network_from_lds)
-      budget -= step_bytes;
-      quad_mask |= 15u << (4 * jl);
-      if (far) quad_far |= 1u << jl;
-      for (int g = 0; g < 4; ++g) {
-        LevelParams& Lv = lp[4 * jl + g];
-        const uint32_t res = Lv.res;
-        Lv.q_off_b = far ? (uint32_t)(end_bytes >> 4) : (uint32_t)end_bytes;
-        Lv.q_my_b = far ? res : res << 4;
-        Lv.q_mz_b = far ? res * res : (res * res) << 4;
-        Lv.q_max = res - 1;
-        end_bytes += (uint64_t)res * res * (res + 1) * 16;
-      }
-    }
-    table_bytes = end_bytes;
+    _Float16* dst = grid16.data() + (size_t)Lv.offset * F;
+    const size_t n = (size_t)Lv.size * F + (Lv.mode == LV_DENSE ? ((size_t)Lv.res * Lv.res + Lv.res + 1) * F : 0);
+    for (size_t i = 0; i < n; ++i) dst[i] = (_Float16)src[i % ((size_t)Lv.size * F)];
   }
   // Uploads go through the context's own stream and the device is drained afterwards: the
   // render stream is non-blocking, so a NULL-stream hipMemcpy gives no ordering against it
@@ -1117,27 +1143,15 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream);
   };
-  // byte-offset constants of level_gather / level_gather_wide / level_gather_f1: an entry is 2 F bytes (the generic instance's
-  // literal index arithmetic, gen_level, does not read them)
-  const uint32_t sh_b = F == 8 ? 4u : (F == 4 ? 3u : (F == 1 ? 1u : 2u));
-  for (LevelParams& L : lp) {
-    const bool hashed_pow2 = L.mode == LV_HASH_POW2;
-    L.off_b = L.offset << sh_b;
-    if (hashed_pow2) {
-      L.my_b = 2654435761u << sh_b;
-      L.mz_b = 805459861u << sh_b;
-    } else {  // the additive multipliers of the stride loop above (dense: res, res^2; LV_ADD_POW2: possibly wrapped / 0)
-      L.my_b = (L.my_b >> 2) << sh_b;
-      L.mz_b = (L.mz_b >> 2) << sh_b;
-    }
-    L.mask_b = (hashed_pow2 || L.mode == LV_ADD_POW2) ? ((L.size - 1) << sh_b) : 0xffffffffu;
-  }
+  std::vector<LevelParams> lp(p.lp, p.lp + 16);
+  uint32_t quad_mask = p.quad_mask, quad_far = p.quad_far;
+  uint64_t table_bytes = p.table_bytes;
   if (hipMalloc(&c->d_grid, table_bytes) != hipSuccess) {  // no room for the copies: the reference-order table alone
     (void)hipGetLastError();
     c->d_grid = nullptr;
     for (LevelParams& Lv : lp) Lv.q_off_b = Lv.q_my_b = Lv.q_mz_b = Lv.q_max = 0;
     quad_mask = quad_far = 0;
-    table_bytes = (uint64_t)grid16.size() * 2;
+    table_bytes = p.table_ref_bytes;
     HIP_TRY(hipMalloc(&c->d_grid, table_bytes));
   }
   HIP_TRY(hipMemcpyAsync(c->d_grid, grid16.data(), grid16.size() * 2, hipMemcpyHostToDevice, c->stream));
@@ -1149,9 +1163,9 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
                                (char*)c->d_grid + q_bytes, c->stream));
   }
   HIP_TRY(upload(&c->d_wfrag, frags.data(), frags.size() * 2));
-  if (generic || wide) HIP_TRY(upload(&c->d_gen, &G, sizeof(G)));
-  if (wide) HIP_TRY(upload(&c->d_wfrag_gen, frags_gen.data(), frags_gen.size() * 2));
-  if (hot_width || wide_sh || hot_grid) HIP_TRY(upload(&c->d_wfrag_hot, frags_hot.data(), frags_hot.size() * 2));
+  if (p.stage != NET_HOT) HIP_TRY(upload(&c->d_gen, &G, sizeof(G)));
+  if (p.stage == NET_WIDE) HIP_TRY(upload(&c->d_wfrag_gen, frags_gen.data(), frags_gen.size() * 2));
+  if (p.own != p.stage) HIP_TRY(upload(&c->d_wfrag_hot, frags_hot.data(), frags_hot.size() * 2));
   HIP_TRY(upload(&c->d_lv, lp.data(), lp.size() * sizeof(LevelParams)));
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipDeviceSynchronize());
@@ -1198,25 +1212,20 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   M.quad_mask = quad_mask;
   M.quad_far = quad_far;
   c->table_bytes = table_bytes;
-  c->table_ref_bytes = (uint64_t)grid16.size() * 2;
+  c->table_ref_bytes = p.table_ref_bytes;
   c->gather_addresses = 0;
   for (uint32_t l = 0; l < L; ++l) c->gather_addresses += ((quad_mask >> l) & 1u) ? 2u : (d->interpolation == NRF_INTERP_NEAREST ? 1u : 8u);
-  M.generic = generic ? 1u : 0u;
-  M.wide = (!generic && wide) ? 1u : 0u;
+  M.stage = (uint32_t)p.stage;
+  M.net = (uint32_t)p.own;  // (set_density_grid falls back to the stage instance when the own one does not fit)
+  c->own_net = p.own;
   M.gen = (const GenModel*)c->d_gen;
-  M.gen_wave_bytes = gen_wave_bytes;
-  M.gen_frag_bytes = generic ? (uint32_t)(frags.size() * 2) : 0u;
-  M.hot_width = hot_width;
-  M.depth_xd = hot_depth ? d->density_hidden_layers - 1 : 0u;
-  M.depth_xr = hot_depth ? d->rgb_hidden_layers - 1 : 0u;
+  M.gen_wave_bytes = p.gen_wave_bytes;
+  M.gen_frag_bytes = p.stage == NET_GENERIC ? (uint32_t)(frags.size() * 2) : 0u;
+  M.depth_xd = (p.own == NET_DEPTH || p.own == NET_ACT) ? d->density_hidden_layers - 1 : 0u;
+  M.depth_xr = (p.own == NET_DEPTH || p.own == NET_ACT) ? d->rgb_hidden_layers - 1 : 0u;
   M.wfrag_hot = (const uint4*)c->d_wfrag_hot;
-  c->model_hot_width = hot_width;
-  c->model_hot_grid = hot_grid;
-  M.hot_grid = hot_grid;
   M.grid_smooth = d->interpolation == NRF_INTERP_SMOOTHSTEP ? 1u : 0u;
   M.grid_nearest = d->interpolation == NRF_INTERP_NEAREST ? 1u : 0u;
-  c->model_wide_sh = wide_sh;
-  M.wide_sh = wide_sh ? 1u : 0u;
   M.dir_w = dir_w;
   c->gen = G;
   // the density grid of the snapshot (nerf_render.cu:447-466) -- or none yet: nrf_generate_density_grid evaluates it
@@ -1226,7 +1235,7 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
     if (rc) { free_model(c); return rc; }
     c->grid_missing = false;
   } else {
-    std::vector<float> empty((size_t)cells, 0.0f);
+    std::vector<float> empty((size_t)d->density_grid_size * d->density_grid_size * d->density_grid_size * d->cascade, 0.0f);
     rc = set_density_grid(c, empty.data(), d->mean_density);
     if (rc) { free_model(c); return rc; }
     c->grid_missing = true;
@@ -1834,13 +1843,29 @@ int nrf_debug_counters(nrf_context* c, unsigned long long out[16]) {
   return NRF_OK;
 }
 
-// Diagnostic (not part of include/nerfhip.h): which kernel instance renders the loaded model -- 0 register-resident,
+// Diagnostic (not part of include/nerfhip.h): which kernel instance renders the loaded model (DevModel::net) -- 0 register-resident,
 // 1 generic, 2 wide, 3 the register-resident instance of another width (16 / 32 / 128 neurons) or depth, 4 its wide form for SH
 // degree 5..8, 5 a GRID instance (base.json's MLPs behind another grid: F = 2 with fewer than 16 levels, F = 4 / 8, Smoothstep);
 // + 16 when the persistent form is used (tests assert that a model runs where it is meant to).
 extern "C" int nrf_debug_instance(nrf_context* c) {
   if (!c || !c->model_loaded) return -1;
-  return (c->dm.wide_sh ? 4 : (c->dm.hot_grid ? 5 : (c->dm.hot_width ? 3 : (c->dm.generic ? 1 : (c->dm.wide ? 2 : 0))))) + (c->dm.persistent ? 16 : 0);
+  const int net = (int)c->dm.net;
+  const int code = net == NET_HOT ? 0 : net == NET_GENERIC ? 1 : net == NET_WIDE ? 2 : net == NET_WIDE_SH ? 4 : net_grid_f(net) ? 5 : 3;
+  return code + (c->dm.persistent ? 16 : 0);
+}
+
+// Diagnostic (not part of include/nerfhip.h): plan_model of a descriptor without a device, at an explicit quad-copy budget (MiB) --
+// out = {own instance, stage instance, quad_mask, quad_far, waves of the own instance's persistent workgroup, its LDS bytes
+// without the march tables}; returns nrf_load_model's status for the descriptor (tests/test_instance_plan_cpu.py)
+extern "C" int nrf_debug_plan(const nrf_model_desc* d, int allow_own, uint64_t budget_mb, uint32_t out[6]) {
+  if (!d || !d->params || !out) return fail(NRF_E_INVALID, "null argument");
+  const ModelPlan p = plan_model(*d, allow_own != 0, budget_mb, 4);
+  if (p.rc) return p.rc;
+  const int waves = render_persist_waves(p.own, march_form(d->density_grid_size, d->cascade, d->bound));
+  const uint32_t v[6] = {(uint32_t)p.own, (uint32_t)p.stage, p.quad_mask, p.quad_far, (uint32_t)waves,
+                         (uint32_t)render_persistent_lds_bytes(p.own, waves, p.gen_wave_bytes)};
+  std::memcpy(out, v, sizeof(v));
+  return NRF_OK;
 }
 
 // Diagnostic build: entry / exit stamps (s_memtime) of the persistent kernel's waves, 2 x n values.
@@ -2060,8 +2085,8 @@ int nrf_encode_grid(nrf_context* c, const void* pos01, uint32_t n, void* out, vo
 // generic-layout fragments; the fused kernel and nrf_network run the wide instance itself.
 static DevModel stage_model(const nrf_context* c) {
   DevModel m = c->dm;
-  if (m.wide) {
-    m.generic = 1u;
+  if (m.stage == NET_WIDE) {
+    m.stage = NET_GENERIC;
     m.wfrag = (const uint4*)c->d_wfrag_gen;
   }
   return m;

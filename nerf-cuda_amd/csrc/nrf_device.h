@@ -103,7 +103,6 @@ static_assert(MlpShape<64>::D1 == FRAG_D1 && MlpShape<64>::R0 == FRAG_R0 && MlpS
 //   (8 fragments each: 2 m + s) | the rgb MLP's 64 -> 64 layers
 enum : int { DF_D0 = 0, DF_D1 = 4, DF_R0 = 6, DF_R2 = 10, DF_WW = 12, DEPTH_MAX_WW = 5, DEPTH_FRAGS = DF_WW + 8 * DEPTH_MAX_WW };
 
-constexpr uint32_t HOT_WIDTH_ACT = 65;  // DevModel::hot_width of the NET_ACT instance (64 neurons, runtime hidden activations)
 struct DevModel {
   const uint32_t* grid;      // half2 entries
   const uint32_t* occ_bits;  // 1 bit per density-grid cell: grid[cell] > min(0.01, mean_density)
@@ -128,16 +127,13 @@ struct DevModel {
   uint32_t rgb_activation, rgb_output_activation;
   uint32_t uni_modes;    // 2 bits per unrolled step jl = 0..3 of the fused kernel (levels 4*jl + g): 0 mixed, 1 all dense,
                          // 2 all power-of-two hashed (host: nrf_load_model)
-  uint32_t generic;      // 0: the shape of the reference's base.json (L = 16, F = 2, 64 neurons, 1 + 2 hidden layers, a
-                         // 16-wide direction encoding -- or a Frequency encoding of up to 80 values: `wide` --, hidden
-                         // ReLU / density output None / sigma Exponential / rgb output None or Sigmoid, linear
-                         // interpolation, every level dense, power-of-two hashed or LV_ADD_POW2): the register-resident
-                         // instance (this file);
-                         // 1: everything else: the generic instance (nrf_generic.h), described by `gen`
+  uint32_t net;          // NET_* (nrf_launch.h): the instance that renders the frames (set_density_grid: the model's own one when its
+                         // march tables fit beside its persistent workgroup, else `stage`)
+  uint32_t stage;        // NET_HOT (the shape of the reference's base.json), NET_WIDE (the same with a Frequency direction encoding
+                         // of 32..80 values) or NET_GENERIC (everything else, nrf_generic.h, described by `gen`): the instance of the
+                         // stage entry points, nrf_network, the per-strip kernel and the density-grid generation (nrf_api.hip plan_model)
   const struct GenModel* gen;  // device memory; nullptr unless generic
   uint32_t gen_wave_bytes;     // generic instance: LDS bytes per wave of the direction rows + activation rows
-  uint32_t wide;               // register-resident instance with a 32..80-wide Frequency direction encoding: the first rgb
-                               // layer takes RK_WIDE K steps, the extra direction entries are evaluated in-lane per sample
   uint32_t coarse_shift;    // 2 or 0
   uint32_t lds_coarse_words;  // words of occ_coarse staged in LDS by render_kernel (0: read it from global)
   uint32_t lds_ctab_floats;   // floats of cell_bound staged in LDS (0: read it from global)
@@ -147,19 +143,11 @@ struct DevModel {
   uint32_t gen_frag_bytes;  // generic instance: bytes of its weight fragments
   uint32_t gen_weights_lds; // generic instance, persistent kernel: the fragments are staged in LDS (they fit beside rows and tables)
   uint32_t n_cus;           // compute units of the device: workgroups of the persistent kernel
-  // a model of the base.json SHAPE with 16 / 32 / 128 neurons: `generic` is set (stage entry points, the per-strip kernel and
-  // the density-grid generation run the generic instance), but its frames are rendered by a register-resident instance of
-  // the persistent kernel of that width, from fragments in the MlpShape<width> order
-  uint32_t hot_width;       // 0, 16, 32 or 128 -- or 64: the DEPTH instance (64 neurons, other numbers of hidden layers: depth_xd / depth_xr)
-                            // -- or 65 (HOT_WIDTH_ACT): 64 neurons with hidden activations other than ReLU, the NET_ACT instance
-  uint32_t depth_xd, depth_xr;  // hot_width == 64: 64 -> 64 layers of the density MLP (hidden layers - 1) and of the rgb MLP (hidden layers - 1)
-  const uint4* wfrag_hot;   // MlpShape<hot_width>::N * 64 uint4; wide_sh: the wide layout (N_FRAGS_WIDE_ALL fragments)
-  uint32_t hot_grid;        // 0, or F = 1 / 2 / 4 / 8 (F = 1: round 5): a grid other than base.json's 16 x 2 -- fewer than 16 levels at F = 2, F = 4 / 8 with up to 32
-                            // features in all, Linear or Smoothstep -- in front of base.json's MLPs: the register-resident GRID instance
-                            // (NET_GRID2 / 4 / 8, persistent kernel only; fragments in wfrag_hot with that grid's K order)
+  uint32_t depth_xd, depth_xr;  // NET_DEPTH / NET_ACT: 64 -> 64 layers of the density MLP (hidden layers - 1) and of the rgb MLP (hidden layers - 1)
+  const uint4* wfrag_hot;   // fragments of a register-resident `net` other than `stage`: MlpShape<net_width(net)>::N * 64 uint4;
+                            // NET_WIDE_SH: the wide layout (N_FRAGS_WIDE_ALL fragments); GRID instances: that grid's K order
   uint32_t grid_smooth;     // the grid interpolates with Smoothstep (GRID instances)
   uint32_t grid_nearest;    // InterpolationType::Nearest (grid.h:215-232): the entry at floor(pos), no weights -- ONE gather per level (GRID instances)
-  uint32_t wide_sh;         // SphericalHarmonics of degree 5..8 on the base.json shape: NET_WIDE_SH renders the frames (persistent kernel)
   uint32_t dir_w;           // padded width of the direction encoding (16 .. 80)
   uint32_t quad_far;        // bit jl: step jl's four levels have FAR quad copies (beyond a buffer resource's 4 GiB: level_gather_quad_far)
   uint32_t quad_mask;       // bit l: level l is gathered from its cell-major quad copy (level_gather_quad); granted four levels -- one unrolled

@@ -67,7 +67,8 @@ __global__ __launch_bounds__(256) void gen_encode_grid_kernel(const DevModel M, 
     const float px = pos01[3 * (size_t)s], py = pos01[3 * (size_t)s + 1], pz = pos01[3 * (size_t)s + 2];
     half_t* row = out + (size_t)s * G.feat_w;
     half_t r[8];
-    if (M.hot_grid != 0u) {
+    const int gf = net_grid_f((int)M.net);
+    if (gf != 0) {
       // the model's frames come from a GRID instance of the render kernel (nrf_render.h grid_features): this entry point then runs
       // THAT instance's gathers and interpolation, so that the bit-exact encode test covers them (tests/test_generic_gpu.py)
       // -- including the specialisation grid_features picks for the level: the render kernel's lane group g holds the levels
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void gen_encode_grid_kernel(const DevModel M, 
       float fr[3];
       uint32_t o[4] = {0u, 0u, 0u, 0u};
       const uint32_t uni = (M.uni_modes >> (2 * (level >> 2))) & 3u;
-      if (M.hot_grid == 1u) {  // F = 1: one half per (sample, level)
+      if (gf == 1) {  // F = 1: one half per (sample, level)
         uint32_t r;
         if (M.grid_nearest) {
           r = uni == 2u ? level_nearest_f1<2>(M.grid, M.grid_bytes, lvs[level], px, py, pz) : level_nearest_f1<0>(M.grid, M.grid_bytes, lvs[level], px, py, pz);
@@ -92,12 +93,12 @@ __global__ __launch_bounds__(256) void gen_encode_grid_kernel(const DevModel M, 
         continue;
       }
       if (M.grid_nearest) {
-        if (M.hot_grid == 2u) {
+        if (gf == 2) {
           uint32_t q[1];
           if (uni == 2u) level_nearest<2, 1>(M.grid, M.grid_bytes, lvs[level], px, py, pz, q);
           else level_nearest<0, 1>(M.grid, M.grid_bytes, lvs[level], px, py, pz, q);
           o[0] = q[0];
-        } else if (M.hot_grid == 4u) {
+        } else if (gf == 4) {
           uint32_t q[2];
           if (uni == 2u) level_nearest<2, 2>(M.grid, M.grid_bytes, lvs[level], px, py, pz, q);
           else level_nearest<0, 2>(M.grid, M.grid_bytes, lvs[level], px, py, pz, q);
@@ -106,13 +107,13 @@ __global__ __launch_bounds__(256) void gen_encode_grid_kernel(const DevModel M, 
           if (uni == 2u) level_nearest<2, 4>(M.grid, M.grid_bytes, lvs[level], px, py, pz, o);
           else level_nearest<0, 4>(M.grid, M.grid_bytes, lvs[level], px, py, pz, o);
         }
-      } else if (M.hot_grid == 2u) {
+      } else if (gf == 2) {
         uint32_t v[8];
         if (uni == 2u) level_gather<2>(M.grid, M.grid_bytes, lvs[level], px, py, pz, v, fr);
         else level_gather<0>(M.grid, M.grid_bytes, lvs[level], px, py, pz, v, fr);
         if (M.grid_smooth) smoothstep_fractions(fr);
         o[0] = level_interp<false>(v, fr);
-      } else if (M.hot_grid == 4u) {
+      } else if (gf == 4) {
         uint32_t v[16], q[2];
         if (uni == 2u) level_gather_wide<2, 2>(M.grid, M.grid_bytes, lvs[level], px, py, pz, v, fr);
         else if (uni == 1u) level_gather_wide<1, 2>(M.grid, M.grid_bytes, lvs[level], px, py, pz, v, fr);
@@ -796,10 +797,7 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     VB.class_cols = (strips_x + N - 1) / N;  // a row holds at most this many of the rank's strips
     if ((long long)q * VB.class_cols >= 0xffffff) return hipErrorInvalidValue;  // 24-bit queue positions
     const int waves = (int)M.persist_waves;
-    const int lds = (M.wide_sh ? render_persistent_lds_widesh_bytes() : M.hot_width ? render_persistent_lds_width_bytes((int)M.hot_width)
-                     : M.hot_grid ? render_persistent_lds_fixed_bytes(0u, 0u, 0u, 16)  // (the hot instance's workgroup)
-                                 : render_persistent_lds_fixed_bytes(M.generic, M.wide, M.gen_wave_bytes, waves)) +
-                    4 * (int)(M.lds_coarse_words + M.lds_ctab_floats + M.lds_dilated_words) +
+    const int lds = render_persistent_lds_bytes((int)M.net, waves, M.gen_wave_bytes) + 4 * (int)(M.lds_coarse_words + M.lds_ctab_floats + M.lds_dilated_words) +
                     (M.gen_weights_lds ? 16 + (int)M.gen_frag_bytes : 0);
     const long long tiles = (long long)P.n_local_tiles * VB.n_views;
     const int wgs = (int)std::max(1LL, std::min((long long)M.n_cus, (tiles + waves - 1) / waves));
@@ -821,11 +819,11 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     const int form = march_form(M.H, M.cascade, M.bound);
     const bool unit = form == MARCH_FORM_UNIT, pow2 = form == MARCH_FORM_POW2;
     const PersistLaunch L{&M, &P, &VB, rgba, depth, counters, queue, st, lds, wgs, waves, unit, pow2};
-    if (M.wide_sh || M.wide) e = launch_persistent_wide(L);   // Frequency / SH directions beyond 16 values (nrf_kernels_wide.hip)
-    else if (M.hot_width) e = launch_persistent_width(L);     // 16 / 32 / 128 neurons, other depths (nrf_kernels_width.hip)
-    else if (M.hot_grid) e = launch_persistent_grid(L);       // other grids in front of base.json's MLPs (nrf_kernels_grid.hip)
-    else if (M.generic) e = launch_persistent_generic(L);     // nrf_kernels_generic.hip
-    else e = launch_persistent_hot(L);                        // the base.json shape (nrf_kernels_hot.hip)
+    if (M.net == NET_HOT) e = launch_persistent_hot(L);                          // the base.json shape (nrf_kernels_hot.hip)
+    else if (M.net == NET_GENERIC) e = launch_persistent_generic(L);             // nrf_kernels_generic.hip
+    else if (M.net == NET_WIDE || M.net == NET_WIDE_SH) e = launch_persistent_wide(L);  // Frequency / SH directions beyond 16 values (nrf_kernels_wide.hip)
+    else if (net_grid_f((int)M.net)) e = launch_persistent_grid(L);             // other grids in front of base.json's MLPs (nrf_kernels_grid.hip)
+    else e = launch_persistent_width(L);                                         // 16 / 32 / 128 neurons, other depths / activations (nrf_kernels_width.hip)
     if (e != hipSuccess) return e;
     return hipGetLastError();
   }
@@ -833,8 +831,8 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     const hipError_t e0 = clear_for_first();
     if (e0 != hipSuccess) return e0;
   }
-  const int fixed = M.generic ? gen_lds_bytes(M, RENDER_WAVES)
-                              : (M.wide ? LDS_FIXED_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + RENDER_WAVES * LDS_RAYD_BYTES
+  const int fixed = M.stage == NET_GENERIC ? gen_lds_bytes(M, RENDER_WAVES)
+                              : (M.stage == NET_WIDE ? LDS_FIXED_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + RENDER_WAVES * LDS_RAYD_BYTES
                                         : LDS_FIXED_BYTES);
   const int lds = fixed + (lds_tab ? 4 * (int)(M.lds_coarse_words + M.lds_ctab_floats) : 0);
   // hot instances: compile-time activations, march tables in LDS; a power-of-two grid with either one cascade and
@@ -855,7 +853,7 @@ hipError_t launch_build_quads(const void* table, uint32_t res, uint32_t size, bo
 
 hipError_t launch_encode_grid(const DevModel& M, const void* pos01, uint32_t n, void* out, hipStream_t st, bool fast_interp) {
   if (!n) return hipSuccess;
-  if (M.generic)
+  if (M.stage == NET_GENERIC)
     hipLaunchKernelGGL(gen_encode_grid_kernel, dim3(grid_for((uint64_t)n * M.n_levels)), dim3(256), 0, st, M, (const float*)pos01, n,
                        (half_t*)out);
   else if (fast_interp)
@@ -869,7 +867,7 @@ hipError_t launch_encode_grid(const DevModel& M, const void* pos01, uint32_t n, 
 
 hipError_t launch_encode_dir(const DevModel& M, const void* dir01, uint32_t n, void* out, hipStream_t st) {
   if (!n) return hipSuccess;
-  if (M.generic)
+  if (M.stage == NET_GENERIC)
     hipLaunchKernelGGL(gen_encode_dir_kernel, dim3(grid_for(n)), dim3(256), 0, st, M, (const float*)dir01, n, (half_t*)out);
   else
     hipLaunchKernelGGL(encode_dir_kernel, dim3(grid_for(n)), dim3(256), 0, st, M, (const float*)dir01, n, (uint32_t*)out);
@@ -879,7 +877,7 @@ hipError_t launch_encode_dir(const DevModel& M, const void* dir01, uint32_t n, v
 hipError_t launch_mlp_forward(const DevModel& M, const void* feat, const void* dirfeat, uint32_t n, void* out, uint32_t repeat,
                               hipStream_t st) {
   if (!n) return hipSuccess;
-  if (M.generic) {
+  if (M.stage == NET_GENERIC) {
     const int lds = gen_lds_bytes(M, 4);
     hipError_t e = allow_lds(gen_mlp_forward_kernel, lds);
     if (e != hipSuccess) return e;
@@ -916,13 +914,13 @@ hipError_t launch_mlp_forward(const DevModel& M, const void* feat, const void* d
 hipError_t launch_network(const DevModel& M, const void* xyz, const void* dir, uint32_t n, void* sigma, void* rgb, hipStream_t st) {
   if (!n) return hipSuccess;
   const uint64_t chunks = ((uint64_t)n + 63) / 64;
-  if (M.generic) {
+  if (M.stage == NET_GENERIC) {
     const int lds = gen_lds_bytes(M, 4);
     hipError_t e = allow_lds(network_kernel<NET_GENERIC>, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(network_kernel<NET_GENERIC>, dim3(grid_for(chunks, 4, 256 * 4)), dim3(256), lds, st, M,
                        (const float*)xyz, (const float*)dir, n, (float*)sigma, (float*)rgb);
-  } else if (M.wide) {
+  } else if (M.stage == NET_WIDE) {
     const int lds = LDS_TOTAL_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + 4 * LDS_RAYD_BYTES;
     hipLaunchKernelGGL(network_kernel<NET_WIDE>, dim3(grid_for(chunks, 4, 256 * 4)), dim3(256), lds, st, M,
                        (const float*)xyz, (const float*)dir, n, (float*)sigma, (float*)rgb);
@@ -1068,32 +1066,15 @@ void preload_kernels(bool all) {
   }
 }
 
-int render_lds_bytes() { return LDS_FIXED_BYTES; }
-// LDS of the persistent workgroup of `waves` waves without its march tables (lds_map<NET> + the queue words)
-int render_persistent_lds_fixed_bytes(uint32_t generic, uint32_t wide, uint32_t gen_wave_bytes, int waves) {
-  if (generic) return LDS_LEVEL_BYTES + waves * ((int)sizeof(WaveLds) + (int)gen_wave_bytes) + LDS_QUEUE_BYTES;
-  if (wide) return LDS_WFRAG_WIDE_BYTES + LDS_LEVEL_BYTES + waves * ((int)sizeof(WaveLds) + LDS_RAYD_BYTES) + LDS_QUEUE_BYTES;
-  return LDS_WFRAG_BYTES + LDS_LEVEL_BYTES + waves * (int)sizeof(WaveLds) + LDS_QUEUE_BYTES;
+int render_persist_waves(int net, int form) {
+  return net == NET_WIDE && form == MARCH_FORM_GENERIC ? WIDE_GENERIC_MARCH_WAVES : persist_waves(net);  // (nrf_kernels_wide.hip)
 }
-// ... of the 16-wave workgroup of a width instance (NET_W16 / NET_W32 / NET_W128)
-static int width_net(int width) {
-  return width == 16 ? NET_W16 : (width == 32 ? NET_W32 : (width == 64 ? NET_DEPTH : (width == (int)HOT_WIDTH_ACT ? NET_ACT : NET_W128)));
+// LDS of the persistent workgroup without its march tables: lds_map<NET> (weight fragments, level table, the waves' blocks and
+// per-wave rows) + the queue words
+int render_persistent_lds_bytes(int net, int waves, uint32_t gen_wave_bytes) {
+  const int wave_rows = net == NET_GENERIC ? (int)gen_wave_bytes : (net == NET_WIDE ? LDS_RAYD_BYTES : (net == NET_WIDE_SH ? LDS_SHROW_BYTES : 0));
+  return (net == NET_GENERIC ? 0 : net_wfrag_bytes(net)) + LDS_LEVEL_BYTES + waves * ((int)sizeof(WaveLds) + wave_rows) + LDS_QUEUE_BYTES;
 }
-int render_persistent_lds_width_bytes(int width) {
-  const int net = width_net(width);
-  return net_wfrag_bytes(net) + LDS_LEVEL_BYTES + persist_waves(net) * (int)sizeof(WaveLds) + LDS_QUEUE_BYTES;
-}
-int render_persist_waves_for(uint32_t generic, uint32_t wide, uint32_t wide_sh, uint32_t hot_width, uint32_t hot_grid, int form) {
-  if (wide_sh) return persist_waves(NET_WIDE_SH);
-  if (hot_grid) return persist_waves(hot_grid == 1 ? NET_GRID1 : (hot_grid == 2 ? NET_GRID2 : (hot_grid == 4 ? NET_GRID4 : NET_GRID8)));
-  if (hot_width) return persist_waves(width_net((int)hot_width));
-  if (wide && !generic && form == MARCH_FORM_GENERIC) return WIDE_GENERIC_MARCH_WAVES;  // (nrf_kernels_wide.hip)
-  return persist_waves(generic ? NET_GENERIC : (wide ? NET_WIDE : NET_HOT));
-}
-int render_persistent_lds_widesh_bytes() {  // the 8-wave workgroup of NET_WIDE_SH without its march tables
-  return net_wfrag_bytes(NET_WIDE_SH) + LDS_LEVEL_BYTES + persist_waves(NET_WIDE_SH) * ((int)sizeof(WaveLds) + LDS_SHROW_BYTES) + LDS_QUEUE_BYTES;
-}
-int render_width_frags(int width) { return width == 16 ? MlpShape<16>::N : (width == 32 ? MlpShape<32>::N : (width == 128 ? MlpShape<128>::N : N_FRAGS)); }
 int render_wide_lds_fixed_bytes() { return LDS_FIXED_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + RENDER_WAVES * LDS_RAYD_BYTES; }
 int render_lds_table_max_bytes() { return LDS_MARCH_TABLE_MAX; }
 int render_gen_lds_fixed_bytes(uint32_t gen_wave_bytes) { return LDS_LEVEL_BYTES + RENDER_WAVES * ((int)sizeof(WaveLds) + (int)gen_wave_bytes); }

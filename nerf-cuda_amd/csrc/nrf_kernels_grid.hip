@@ -12,10 +12,10 @@ namespace nrf {
   } while (0)
 
 hipError_t launch_persistent_grid(const PersistLaunch& L) {
-  const uint32_t f = L.M->hot_grid;
-  if (f == 1) NRF_LAUNCH_GRID(NET_GRID1);
-  else if (f == 2) NRF_LAUNCH_GRID(NET_GRID2);
-  else if (f == 4) NRF_LAUNCH_GRID(NET_GRID4);
+  const uint32_t net = L.M->net;
+  if (net == NET_GRID1) NRF_LAUNCH_GRID(NET_GRID1);
+  else if (net == NET_GRID2) NRF_LAUNCH_GRID(NET_GRID2);
+  else if (net == NET_GRID4) NRF_LAUNCH_GRID(NET_GRID4);
   else NRF_LAUNCH_GRID(NET_GRID8);
   return hipGetLastError();
 }

@@ -23,14 +23,14 @@ namespace nrf {
 hipError_t launch_strip(const StripLaunch& L) {
   if (L.perturb) {  // nrf_options.perturb > 0 (render_utils.h:585-589): three instances of their own, march tables in global memory
     if (L.lds_tab) return hipErrorInvalidConfiguration;
-    if (L.M->generic) NRF_LAUNCH_RENDER_PERTURB(NET_GENERIC);
-    else if (L.M->wide) NRF_LAUNCH_RENDER_PERTURB(NET_WIDE);
+    if (L.M->stage == NET_GENERIC) NRF_LAUNCH_RENDER_PERTURB(NET_GENERIC);
+    else if (L.M->stage == NET_WIDE) NRF_LAUNCH_RENDER_PERTURB(NET_WIDE);
     else NRF_LAUNCH_RENDER_PERTURB(NET_HOT);
     return hipGetLastError();
   }
-  if (L.M->generic) {
+  if (L.M->stage == NET_GENERIC) {
     if (L.lds_tab) NRF_LAUNCH_RENDER(NET_GENERIC, true, MARCH_GENERIC); else NRF_LAUNCH_RENDER(NET_GENERIC, false, MARCH_GENERIC);
-  } else if (L.M->wide) {
+  } else if (L.M->stage == NET_WIDE) {
     if (L.unit) NRF_LAUNCH_RENDER(NET_WIDE, true, MARCH_UNIT);
     else if (L.pow2) NRF_LAUNCH_RENDER(NET_WIDE, true, MARCH_POW2);
     else if (L.lds_tab) NRF_LAUNCH_RENDER(NET_WIDE, true, MARCH_GENERIC);

@@ -5,7 +5,7 @@
 namespace nrf {
 
 hipError_t launch_persistent_wide(const PersistLaunch& L) {
-  if (L.M->wide_sh) {
+  if (L.M->net == NET_WIDE_SH) {
     if (L.unit) NRF_LAUNCH_PERSISTENT(NET_WIDE_SH, MARCH_UNIT); else NRF_LAUNCH_PERSISTENT(NET_WIDE_SH, MARCH_GENERIC);
   } else {
     if (L.unit) NRF_LAUNCH_PERSISTENT(NET_WIDE, MARCH_UNIT);

@@ -5,6 +5,24 @@
 #include <stdint.h>
 
 namespace nrf {
+// Instances of the render kernel (nrf_render.h), one id for host and device code.  DevModel::net renders the frames;
+// DevModel::stage (NET_HOT, NET_WIDE or NET_GENERIC) runs the stage entry points, the per-strip kernel and the density-grid
+// generation, and renders the frames when the model's own instance does not fit (nrf_api.hip plan_model, set_density_grid).
+// NET_W16 / NET_W32 / NET_W128: the register-resident instance for the other widths of tcnn's FullyFusedMLP (persistent kernel only)
+// NET_WIDE_SH: the wide form for SphericalHarmonics of degree 5..8 (32..64 direction values): the entries beyond the first sixteen
+// are computed once per ray into an LDS row (not per sample in-lane as for Frequency) -- persistent kernel only
+// NET_DEPTH: 64 neurons with other numbers of hidden layers than base.json's 1 + 2 (mlp_tiles_depth) -- persistent kernel only
+// NET_ACT (round 6): the same with hidden activations other than ReLU (Squareplus, Softplus, Sigmoid, Exponential, None: activate_native
+// on the fp32 accumulators) -- 12 waves per workgroup: the activation sequences need the registers
+// NET_GRID1 / 2 / 4 / 8: base.json's MLPs behind another grid -- F = 1, F = 2 with fewer than 16 levels, F = 4 / 8 with up to 32
+// features in all, Linear, Smoothstep or Nearest (grid_features) -- persistent kernel only
+enum : int { NET_HOT = 0, NET_GENERIC = 1, NET_WIDE = 2, NET_W16 = 3, NET_W32 = 4, NET_W128 = 5, NET_WIDE_SH = 6, NET_DEPTH = 7,
+             NET_GRID2 = 8, NET_GRID4 = 9, NET_GRID8 = 10, NET_GRID1 = 11, NET_ACT = 12 };
+__host__ __device__ constexpr int net_grid_f(int net) {
+  return net == NET_GRID2 ? 2 : (net == NET_GRID4 ? 4 : (net == NET_GRID8 ? 8 : (net == NET_GRID1 ? 1 : 0)));
+}
+__host__ __device__ constexpr int net_width(int net) { return net == NET_W16 ? 16 : (net == NET_W32 ? 32 : (net == NET_W128 ? 128 : 64)); }
+
 struct DevModel;
 struct FrameParams;
 struct ViewBatch;
@@ -53,17 +71,12 @@ inline int march_form(uint32_t H, uint32_t cascade, float bound) {
   if (pow2_h && cascade > 1 && bound >= 1.0f && frexpf(bound, &eb) == 0.5f) return MARCH_FORM_POW2;    // several, power-of-two bound
   return MARCH_FORM_GENERIC;
 }
-// waves of the persistent workgroup of the instance that renders such a model (hot_width: 0 or 16 / 32 / 64 / 128; hot_grid: 0 or the
-// F of a GRID instance); the generic
-// instance may also run WITH 8 (set_density_grid tries 12 first)
-int render_persist_waves_for(uint32_t generic, uint32_t wide, uint32_t wide_sh, uint32_t hot_width, uint32_t hot_grid, int form);
+// waves of the persistent workgroup of instance `net` with that march form (NET_GENERIC may also run with 8: set_density_grid
+// tries 12 first), and its LDS bytes without the march tables (gen_wave_bytes: the generic instance's per-wave rows)
+int render_persist_waves(int net, int form);
+int render_persistent_lds_bytes(int net, int waves, uint32_t gen_wave_bytes);
 // loads the code objects of the render kernel's instance families now instead of at their first launch
 void preload_kernels(bool all);
-int render_lds_bytes();
-int render_persistent_lds_fixed_bytes(uint32_t generic, uint32_t wide, uint32_t gen_wave_bytes, int waves);
-int render_persistent_lds_width_bytes(int width);  // LDS of a width instance's persistent workgroup (16 waves) without its march tables
-int render_persistent_lds_widesh_bytes();
-int render_width_frags(int width);                 // weight fragments of MlpShape<width>
 int render_lds_table_max_bytes();
 int render_wide_lds_fixed_bytes();  // wide instance: LDS of render_kernel without the march tables
 int render_gen_lds_fixed_bytes(uint32_t gen_wave_bytes);  // generic instance: LDS of render_kernel without the march tables

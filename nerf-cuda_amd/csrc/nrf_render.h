@@ -45,23 +45,9 @@ struct WaveLds {
 static_assert(sizeof(WaveLds) == 2048 + 24 * SLOTS, "WaveLds layout");
 
 constexpr int LDS_WFRAG_BYTES = N_FRAGS * 64 * 16;  // 20480
-// network instances of the kernels below
-// NET_W16 / NET_W32 / NET_W128: the register-resident instance for the other widths of tcnn's FullyFusedMLP (persistent kernel only)
-// NET_WIDE_SH: the wide form for SphericalHarmonics of degree 5..8 (32..64 direction values): the entries beyond the first sixteen
-// are computed once per ray into an LDS row (not per sample in-lane as for Frequency) -- persistent kernel only
-// NET_DEPTH: 64 neurons with other numbers of hidden layers than base.json's 1 + 2 (mlp_tiles_depth) -- persistent kernel only
-// NET_ACT (round 6): the same with hidden activations other than ReLU (Squareplus, Softplus, Sigmoid, Exponential, None: activate_native
-// on the fp32 accumulators) -- 12 waves per workgroup: the activation sequences need the registers
-// NET_GRID2 / 4 / 8: base.json's MLPs behind another grid -- F = 2 with fewer than 16 levels, F = 4 / 8 with up to 32 features in all,
-// Linear or Smoothstep (grid_features) -- persistent kernel only
-enum : int { NET_HOT = 0, NET_GENERIC = 1, NET_WIDE = 2, NET_W16 = 3, NET_W32 = 4, NET_W128 = 5, NET_WIDE_SH = 6, NET_DEPTH = 7,
-             NET_GRID2 = 8, NET_GRID4 = 9, NET_GRID8 = 10, NET_GRID1 = 11, NET_ACT = 12 };
-__host__ __device__ constexpr int net_grid_f(int net) {
-  return net == NET_GRID2 ? 2 : (net == NET_GRID4 ? 4 : (net == NET_GRID8 ? 8 : (net == NET_GRID1 ? 1 : 0)));
-}
+// network instances of the kernels below: NET_* (nrf_launch.h)
 constexpr int SH_ROW_HALVES = 72;                     // a ray's row: up to 64 direction values + 8 halves of padding (rows 4 banks apart)
 constexpr int LDS_SHROW_BYTES = 64 * SH_ROW_HALVES * 2;  // 9216 per wave
-__host__ __device__ constexpr int net_width(int net) { return net == NET_W16 ? 16 : (net == NET_W32 ? 32 : (net == NET_W128 ? 128 : 64)); }
 __host__ __device__ constexpr int net_wfrag_bytes(int net) {  // weight fragments a workgroup keeps in LDS
   return (net == NET_WIDE || net == NET_WIDE_SH) ? (N_FRAGS + 4 * (RK_WIDE - 1)) * 1024
        : net == NET_W16 ? MlpShape<16>::N * 1024 : net == NET_W32 ? MlpShape<32>::N * 1024 : net == NET_W128 ? MlpShape<128>::N * 1024
