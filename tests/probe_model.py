@@ -1,0 +1,287 @@
+"""Probe models: models whose rendered frame shows single encoding values exactly (helper of test_probe_cpu.py and
+test_probe_gpu.py; no test in it).
+
+A probe model is any model `models.build_model` makes with its MLP parameters and one table feature replaced:
+
+  * every weight matrix is zero except for single routes of weight +1 / -1, each through its own neuron per layer (a seeded
+    permutation: asymmetric), so that rgb[c] = act(s_c * v_c) for one chosen grid feature (through the density MLP into one of
+    g[1..15], then through the rgb MLP) or one chosen direction-encoding value.  The sign sits on the route's first weight.
+    Every sum has one non-zero product: the summation order of an MFMA cannot matter, every fp16 rounding is an identity;
+  * all entries of one grid feature that no route shows (`info["sigma_feature"]`: feature 0 of level 0, or the next one when
+    a route shows feature 0) are 1.0 and routed with weight 11 to g[0]: sigma = exp(11) at every sample, alpha == 1.0f with
+    any exp, a ray ends at its first sample with weight exactly 1.
+
+So for every ray that meets occupied space: pixel rgb == the fp16 value of the chosen features at the ray's first march
+sample, bit for bit, and alpha == 1.  Hidden activation ReLU (rgb = relu(s v)) or None (rgb = s v); rgb output None.
+
+LEGS lists what the GPU file renders and the CPU file proves its conditions for."""
+from __future__ import annotations
+
+import numpy as np
+
+import models
+import nerfhip as nh
+import synthetic as syn
+
+# instance ids (csrc/nrf_launch.h), as in test_instance_plan_cpu.py
+HOT, GENERIC, WIDE, W16, W32, W128, WIDE_SH, DEPTH, GRID2, GRID4, GRID8, GRID1, ACT = range(13)
+# nrf_debug_instance's class of an instance
+INSTANCE_CLASS = {HOT: 0, GENERIC: 1, WIDE: 2, W16: 3, W32: 3, W128: 3, DEPTH: 3, ACT: 3, WIDE_SH: 4, GRID1: 5, GRID2: 5, GRID4: 5, GRID8: 5}
+
+FRAME_W, FRAME_H = 64, 48
+SH_C0 = np.float16(0.28209479177387814)  # the degree-0 coefficient: the one direction value that is a constant by definition
+
+
+def poses(n=2):
+    """An orbit pose and a camera inside the volume (test_persistent_gpu._poses("inside", 1)[0]), which look in opposite
+    directions: between them every direction value a reduced route set shows takes both signs.  n = 3 (the full legs): one more
+    orbit pose, with which that holds for every spherical-harmonics coefficient up to degree 8; n = 4 (Nearest legs, whose
+    coarse levels show one table entry per cell): another one, for 300 distinct cells of the coarsest level."""
+    return [syn.orbit_pose(222.0, -25.0), syn.orbit_pose(0.0, 20.0, radius=0.4 / 0.33), syn.orbit_pose(90.0, -30.0),
+            syn.orbit_pose(310.0, 40.0)][:n]
+
+
+def random_density_grid(H, cascade, seed, occupied=0.03):
+    """A seeded grid with 3 % of every cascade's cells occupied: first samples spread through the volume."""
+    rng = np.random.default_rng(seed)
+    return (rng.random(cascade * H ** 3) < occupied).astype(np.float32)
+
+
+_BUILT = {}
+NGP_AABB32 = "instant-ngp, aabb_scale 32"
+
+
+def _build(build_kw):
+    """models.build_model, once per shape (a leg loads several probe models of one shape; nothing of the result is written to)."""
+    key = tuple(sorted(build_kw.items()))
+    if key not in _BUILT:
+        _BUILT.clear()  # (legs of one shape follow each other: one shape's arrays are enough to keep)
+        _BUILT[key] = models.build_model(**resolve(build_kw))
+    return _BUILT[key]
+
+
+def resolve(build_kw):
+    """build_model's keywords with instant-ngp's per_level_scale at aabb_scale 32 worked out (by the library: not at import)."""
+    kw = dict(build_kw)
+    if kw.get("per_level_scale") == NGP_AABB32:
+        kw["per_level_scale"] = nh.default_per_level_scale(32.0, 16, 16)
+    return kw
+
+
+def probe_desc(build_kw, routes, density_grid=None, seed=0):
+    """routes: three of ("grid", feature index, sign) / ("dir", value index, sign), one per colour channel.
+    density_grid: None (the synthetic object) or "random" (random_density_grid).  Returns (desc, keep, info)."""
+    assert len(routes) == 3
+    desc, keep, cfg = _build(build_kw)
+    feat_raw, feat_w, width, dens_hidden, rgb_hidden, dir_raw, dir_w = shape = syn.network_shape(cfg)
+    act = cfg["network"]["activation"]
+    assert act in ("ReLU", "None") and cfg["rgb_network"]["activation"] == act and cfg["rgb_network"]["output_activation"] == "None"
+    shown = {k for kind, k, _ in routes if kind == "grid"}
+    sigma_feature = min(k for k in range(feat_raw) if k not in shown)
+    rng = np.random.default_rng(seed)
+    sh = cfg["dir_encoding"]["nested"][0]["otype"] == "SphericalHarmonics"
+    dir_pad = dir_w - dir_raw if sh else 0  # the padding ones of a SphericalHarmonics encoding come first, any other's last
+
+    def matrices(n_in, hidden):
+        dims = [n_in] + [width] * hidden + [16]
+        return [np.zeros((dims[i + 1], dims[i]), np.float32) for i in range(len(dims) - 1)]
+
+    D, R = matrices(feat_w, dens_hidden), matrices(16 + dir_w, rgb_hidden)
+    # a layer's routes run through different neurons: the first four of a seeded permutation (path 0: sigma)
+    d_neurons = [rng.permutation(width)[:4] for _ in range(dens_hidden)]
+    r_neurons = [rng.permutation(width)[:3] for _ in range(rgb_hidden)]
+    g_slots = 1 + rng.permutation(15)[:3]  # the density outputs g[1..15] the grid routes pass through
+
+    def chain(mats, neurons, path, col, row, first, last=1.0):
+        """column `col` of the first matrix -> the path's neuron of every hidden layer -> row `row` of the last matrix"""
+        for i, m in enumerate(mats):
+            out = row if i == len(mats) - 1 else int(neurons[i][path])
+            m[out, col] = (first if i == 0 else 1.0) * (last if i == len(mats) - 1 else 1.0)
+            col = out
+
+    chain(D, d_neurons, 0, sigma_feature, 0, 1.0, last=11.0)
+    for c, (kind, k, sign) in enumerate(routes):
+        assert sign in (1, -1)
+        if kind == "grid":
+            assert 0 <= k < feat_raw
+            chain(D, d_neurons, 1 + c, k, int(g_slots[c]), float(sign))
+            chain(R, r_neurons, c, int(g_slots[c]), c, 1.0)
+        else:
+            assert kind == "dir" and 0 <= k < dir_raw
+            chain(R, r_neurons, c, 16 + dir_pad + k, c, float(sign))
+    mlp = np.concatenate([m.reshape(-1) for m in D + R])
+    params = keep[0].copy()
+    assert nh.expected_n_params(desc) == params.size
+    params[:mlp.size] = mlp
+    lt = nh.level_table(desc)
+    F = int(desc.n_features_per_level)
+    level, f = divmod(sigma_feature, F)
+    table = params[mlp.size:].reshape(-1, F)
+    assert table.shape[0] == int(lt.offset[desc.n_levels])
+    table[int(lt.offset[level]):int(lt.offset[level + 1]), f] = 1.0
+    grid = keep[1]
+    if density_grid == "random":
+        grid = random_density_grid(int(desc.density_grid_size), int(desc.cascade), 77)
+        cfg = dict(cfg, snapshot=dict(cfg["snapshot"], mean_density=float(grid.mean())))
+    else:
+        assert density_grid is None
+    desc2, keep2 = nh.desc_from_config(cfg, params, grid)
+    info = dict(routes=list(routes), bound=float(desc2.bound), act=act, sigma_feature=sigma_feature, shape=shape, F=F,
+                n_levels=int(desc2.n_levels), frequency=cfg["dir_encoding"]["nested"][0]["otype"] == "Frequency",
+                sh=sh, dir_pad=dir_pad)
+    return desc2, keep2, info
+
+
+def pos01(xyz, bound):
+    """World position -> [0, 1]: the one statement kernel (nrf_render.h sample_pos01) and oracle (network_one) share, in fp32:
+    the product by float(1 / (2 bound)) rounded, then + 0.5 rounded."""
+    w = np.float32(1.0 / (2.0 * float(bound)))
+    return (w * np.asarray(xyz, np.float32)).astype(np.float32) + np.float32(0.5)
+
+
+def dir01(d):
+    return (np.float32(0.5) * np.asarray(d, np.float32)).astype(np.float32) + np.float32(0.5)
+
+
+def expected_values(oracle, xyz, dirs, info):
+    """act(s * f16 encoding value) of the three routes at world positions / directions, float32 [n][3]."""
+    feat = oracle.encode_grid(pos01(xyz, info["bound"])).view(np.float16).astype(np.float32)
+    dirf = oracle.encode_dir(dir01(dirs)).view(np.float16).astype(np.float32)
+    want = np.empty((len(feat), 3), np.float32)
+    for c, (kind, k, sign) in enumerate(info["routes"]):
+        v = np.float32(sign) * (feat[:, k] if kind == "grid" else dirf[:, info["dir_pad"] + k])
+        want[:, c] = np.maximum(v, np.float32(0.0)) if info["act"] == "ReLU" else v
+    return want
+
+
+def first_samples(oracle, cam, pose, W, H, opts=None):
+    """(hit [n], xyz [n][3], dirs [n][3], deltas [n][2]) of every ray's first march sample, rays in pixel order."""
+    o, d, nr, fr = oracle.generate_rays(cam, pose, W, H, opts)
+    xyz, dirs, deltas = oracle.march(o, d, nr, fr, 1, opts)
+    hit = deltas[:, 0, 0] > 0
+    xyz, dirs = np.where(hit[:, None], xyz[:, 0], np.float32(0.0)), np.where(hit[:, None], dirs[:, 0], np.float32(0.0))
+    return hit, xyz.astype(np.float32), dirs.astype(np.float32), deltas[:, 0]
+
+
+def expected_rgb(oracle, cam, pose, W, H, info, opts=None):
+    """(hit_mask [H][W], want_rgb [H][W][3]; rays that miss: 0).  The oracle's whole network on the first samples must
+    return the same values exactly: that checks this file's position map and routing against the oracle's."""
+    hit, xyz, dirs, _ = first_samples(oracle, cam, pose, W, H, opts)
+    want = expected_values(oracle, xyz, dirs, info)
+    sigma, rgb = oracle.network(xyz, dirs)
+    assert np.array_equal(rgb[hit], want[hit]) and np.all(sigma[hit] > 5e4)
+    want[~hit] = 0.0
+    return hit.reshape(H, W), want.reshape(H, W, 3)
+
+
+# --------------------------------------------------------------------------- routes
+def reduced_routes(n_levels, F, dir_raw, start=0):
+    """Every grid level once, alternating feature 0 / 1 and the sign from level to level (F = 1: feature 0), then two
+    direction values, the last raw one among them; in threes (one model each), the last model padded with further features."""
+    r = [("grid", l * F + ((l + start) % 2 if F > 1 else 0), 1 if (l + start) % 2 == 0 else -1) for l in range(n_levels)]
+    r += [("dir", dir_raw - 1, 1), ("dir", (1 + start) % max(dir_raw - 1, 1), -1)]
+    k = 0
+    while len(r) % 3:
+        r.append(("grid", (n_levels * F - 1 - k) % (n_levels * F), 1 if k else -1))
+        k += 1
+    return [r[i:i + 3] for i in range(0, len(r), 3)]
+
+
+def full_routes(feat_raw, dir_raw):
+    """Every grid feature and every direction value in both signs."""
+    r = [(kind, k, s) for kind, n in (("grid", feat_raw), ("dir", dir_raw)) for k in range(n) for s in (1, -1)]
+    assert len(r) % 3 == 0
+    return [r[i:i + 3] for i in range(0, len(r), 3)]
+
+
+# --------------------------------------------------------------------------- legs
+T12 = dict(log2_hashmap_size=12, H=32)
+STRIP, PERSISTENT = {"NRF_PERSISTENT": "0"}, {"NRF_PERSISTENT": "1"}
+# gather forms of the 16 x 2 instances: (environment, nrf_model_desc.gather_copy_budget_mb, lane addresses per sample).  "None" must
+# be none for every geometry (a budget of 1 MB still grants step 0 of a base_resolution 8 grid): the environment's 0.
+GATHER = {"none": ({"NRF_QUAD_BUDGET_MB": "0"}, 0, 128), "near": ({}, 256, 80), "far": ({}, 6000, 56)}
+NO_GATHER_AXIS = {"-": ({}, 0, None)}
+
+# name -> (build_model keywords, own instance, stage instance, extra environment)
+INSTANCES = {
+    "hot": ({}, HOT, HOT, {}),
+    "wide_freq12": (dict(dir_otype="Frequency", n_frequencies=12), WIDE, WIDE, {}),
+    "widesh_5": (dict(sh_degree=5), WIDE_SH, GENERIC, {}),
+    "widesh_8": (dict(sh_degree=8), WIDE_SH, GENERIC, {}),
+    "w16": (dict(n_neurons=16), W16, GENERIC, {}),
+    "w32": (dict(n_neurons=32), W32, GENERIC, {}),
+    "w128": (dict(n_neurons=128), W128, GENERIC, {}),
+    "depth_d2_2": (dict(density_hidden_layers=2, rgb_hidden_layers=2), DEPTH, GENERIC, {}),
+    "depth_d3_4": (dict(density_hidden_layers=3, rgb_hidden_layers=4), DEPTH, GENERIC, {}),
+    "depth_d1_1": (dict(density_hidden_layers=1, rgb_hidden_layers=1), DEPTH, GENERIC, {}),
+    "act_none": (dict(activation="None"), ACT, GENERIC, {}),
+    # GRID_SHAPES of test_generic_gpu.py
+    "grid1_g1_16": (dict(n_features_per_level=1), GRID1, GENERIC, {}),
+    "grid2_g2_11": (dict(n_levels=11), GRID2, GENERIC, {}),
+    "grid4_g4_8": (dict(n_features_per_level=4, n_levels=8), GRID4, GENERIC, {}),
+    "grid8_g8_4": (dict(n_features_per_level=8, n_levels=4), GRID8, GENERIC, {}),
+    "grid4_g4_6s": (dict(n_features_per_level=4, n_levels=6, interpolation="Smoothstep"), GRID4, GENERIC, {}),
+    "grid2_g2_16n": (dict(interpolation="Nearest"), GRID2, GENERIC, {}),
+    "generic_w32_width_instances_off": (dict(n_neurons=32), GENERIC, GENERIC, {"NRF_WIDTH_INSTANCES": "0"}),
+    "generic_w32_h2": (dict(n_neurons=32, density_hidden_layers=2), GENERIC, GENERIC, {}),
+}
+QUAD_INSTANCES = ("hot", "wide_freq12", "widesh_5", "widesh_8", "w16", "w32", "w128", "depth_d2_2", "depth_d3_4", "depth_d1_1", "act_none")
+GEOMETRIES = {
+    "base8": dict(base_resolution=8),
+    "base12_pls1.3": dict(base_resolution=12, per_level_scale=1.3),
+    "bound4_cascade3": dict(bound=4.0, cascade=3),
+    "ngp_aabb32": dict(bound=16.0, cascade=5, per_level_scale=NGP_AABB32),
+}
+OPTIONS = ("perturb5", "u8", "views3", "shard1of3")
+
+
+def _leg(name, kw, own, stage, env, gather, routes, grid, option=None):
+    genv, budget, addresses = dict(GATHER, **NO_GATHER_AXIS)[gather]
+    return dict(id=name, build_kw=dict(T12, **kw), own=own, stage=stage, env=dict(env, **genv), budget_mb=budget,
+                addresses=addresses, routes=routes, density_grid=grid, option=option, full=False, n_poses=2)
+
+
+def _legs():
+    out, n = [], 0
+    for name, (kw, own, stage, env) in INSTANCES.items():
+        feat_raw, _, _, _, _, dir_raw, _ = syn.network_shape(syn.base_config(**kw))
+        F = kw.get("n_features_per_level", 2)
+        forms = ("none", "near", "far") if name in QUAD_INSTANCES else ("-",)
+        for sched_name, sched in (("persistent", PERSISTENT), ("strip", STRIP)):
+            for form in forms:
+                if form == "far" and own == WIDE:
+                    continue  # NET_WIDE has no far form
+                n += 1  # the random grid in every other leg, another start of the alternation from leg to leg
+                nearest = kw.get("interpolation") == "Nearest"  # (few cells of a coarse level lie on the object's surface: random grid)
+                out.append(dict(_leg(f"{name}-{sched_name}-{form}" if form != "-" else f"{name}-{sched_name}", kw, own, stage,
+                                     dict(env, **sched), form, reduced_routes(feat_raw // F, F, dir_raw, start=n % 2),
+                                     "random" if n % 2 or nearest else None), n_poses=4 if nearest else 2))
+    for gname, kw in GEOMETRIES.items():
+        n += 1
+        # (how many steps 256 MB hold depends on the geometry: the addresses follow from the plan)
+        out.append(dict(_leg(f"hot-geometry-{gname}", kw, HOT, HOT, PERSISTENT, "near", reduced_routes(16, 2, 16, start=n % 2),
+                             "random" if n % 2 else None), addresses=None))
+    for opt in OPTIONS:
+        n += 1
+        out.append(_leg(f"hot-option-{opt}", {}, HOT, HOT, PERSISTENT, "near", reduced_routes(16, 2, 16, start=n % 2),
+                        "random" if n % 2 else None, option=opt))
+    for form in ("none", "far"):
+        out.append(dict(_leg(f"hot-full-{form}", {}, HOT, HOT, PERSISTENT, form, full_routes(32, 16), "random" if form == "far" else None),
+                        full=True, n_poses=3))
+    return out
+
+
+LEGS = _legs()
+
+
+def leg_options(leg):
+    o = nh.default_options()
+    if leg["option"] == "perturb5":
+        o.perturb = 5
+    return o
+
+
+def leg_models(leg):
+    """(desc, keep, info) of every model of a leg, one per three routes."""
+    for i, routes in enumerate(leg["routes"]):
+        yield probe_desc(leg["build_kw"], routes, leg["density_grid"], seed=1000 + i)
