@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define NRF_ABI_VERSION 6
+#define NRF_ABI_VERSION 7
 #define NRF_MAX_VIEWS 128 /* cameras one launch of the fused kernel takes (nrf_render_views) */
 
 /* ---- status codes ------------------------------------------------------ */
@@ -283,6 +283,24 @@ int nrf_render_views(nrf_context* ctx, int n_views, const float* cams, const flo
 /* SURVEY.md 8(b) lists this entry point as nrf_render_batch: same function.   */
 int nrf_render_batch(nrf_context* ctx, int n_views, const float* cams, const float* poses,
                      void* stream, nrf_frame* out);
+/* (ABI 7) Frames from caller-supplied rays -- whatever a pinhole cannot describe: lens distortion, fisheye, panoramas,
+ * orthographic views, per-eye offsets, the secondary rays of a renderer that mixes a NeRF into its scene.
+ * rays_o, rays_d: device fp32 [n_views][rays_per_view][3], in the space and layout nrf_generate_rays writes (ngp units,
+ * row-major pixels).  The frame is the W x H of nrf_set_resolution: pixel (px, py) of view v takes ray
+ * v * rays_per_view + py * W + px; 1 <= rays_per_view <= W * H, and a pixel whose ray number is >= rays_per_view has
+ * no ray and is the background (rgb = bg_color, alpha 0, depth 0) -- a list of N rays is a W x ceil(N / W) frame.
+ * Everything after ray generation is nrf_render's: near / far against the aabb with min_near, the occupied-box clip
+ * and the visibility walk, march, network, compositing, the get_image_and_depth epilogue; the rays nrf_generate_rays
+ * writes for a camera render that camera's nrf_render frame bit for bit.  Directions are used as given, NOT normalised:
+ * depth and step sizes are in units of t along d, as in the reference.
+ * Ray guard (in the kernel, per ray): a ray with a non-finite component, with |o| > 4096 (see nrf_render) or with |d|^2
+ * outside [0.25, 4] is not marched; its pixel is the background.  Zero components of d are legal.
+ * Honoured: bg_color, min_near, dt_gamma, max_steps, density_scale, shard_* (every rank is given the same arrays and reads
+ * the rays of its own strips), tile_major; bound outputs; nrf_set_max_views; stream / sync rules and the 16 calls in
+ * flight; nrf_get_stats; nrf_read_*.  perturb > 0: NRF_E_UNSUPPORTED.  fast_interp is ignored: the ray instances of the
+ * fused kernel render with the exact arithmetic.  The arrays must stay valid until the call has completed.          */
+int nrf_render_rays(nrf_context* ctx, int n_views, const void* rays_o, const void* rays_d,
+                    uint64_t rays_per_view, void* stream, nrf_frame* out);
 /* Binds caller-owned device buffers (e.g. a render buffer's RGBA plane or a
  * torch tensor) as the target of subsequent nrf_render calls: rgba float
  * [n_px][4], depth float [n_px], n_px as nrf_frame describes.  NULL, NULL

@@ -468,6 +468,7 @@ struct nrf_context {
   void* d_ctab = nullptr;
   void* d_gen = nullptr;
   void* d_wfrag_gen = nullptr;  // wide models: generic-layout fragments for the stage entry points
+  bool rays_persistent = false; // nrf_render_rays runs the persistent RAYS instance (it exists for the hot shape only: set_density_grid), else the per-strip one
   int own_net = NET_HOT;        // the loaded model's own instance (plan_model): set_density_grid checks for every grid whether it fits
   void* d_wfrag_hot = nullptr;  // fragments of the model's own register-resident instance when it is not the stage one
   GenModel gen{};  // host copy of the generic instance's description (valid unless dm.stage == NET_HOT)
@@ -909,6 +910,9 @@ int set_density_grid(nrf_context* c, const float* density_grid, float mean_densi
       if (M.persistent) break;
     }
   }
+  // caller-supplied rays (nrf_render_rays): the persistent RAYS instance is the hot shape's; every other model -- and a hot one
+  // whose tables do not fit -- renders rays in the per-strip RAYS instance of its stage (nrf_kernels_rays.hip)
+  c->rays_persistent = M.persistent != 0 && M.net == NET_HOT;
   c->desc.mean_density = mean_density;
   c->host_grid.assign(density_grid, density_grid + cells);
   return NRF_OK;
@@ -1361,16 +1365,40 @@ void roi_cols(const int roi[4], int W, int& x0, int& x1) {
 // next slot of the context's ring of statistics counters + work queues (cleared on the call's own stream), so calls of
 // one context that overlap on different streams never share a queue.
 // rows_out (optional): per view the rows [lo, hi) and the columns [x0, x1) (whole tiles) its region of interest covers.
-constexpr float MAX_CAMERA_DISTANCE = 4096.0f;  // in the reference's ngp units (0.33 x the nerf pose's + 0.5), see render_views_impl
+// (MAX_CAMERA_DISTANCE, and the guard of caller-supplied rays beside it: nrf_device.h)
 struct ProgressArgs {
   unsigned* done;   // device [n_views][tiles_y], zeroed on the stream before the launches
   unsigned* flags;  // pinned host [n_views][tiles_y]
   unsigned epoch;
 };
+// rays (nrf_render_rays): the views' rays come from the caller's arrays -- cams / poses are null, every view's region of interest
+// is its whole frame, and the launch is neither planned (there is no camera to price strips from) nor a host frame.
+struct RayArgs {
+  const float *o, *d;  // device [n_views][per_view][3]
+  uint64_t per_view;
+};
+// The model as the RAYS instances see it: the persistent form for the hot shape only (nrf_context::rays_persistent); the per-strip
+// kernel borrows the weight area for the dilated table, so it is given what fits there (as set_density_grid decides without the
+// persistent form).
+DevModel rays_model(const nrf_context* c) {
+  DevModel m = c->dm;
+  if (!c->rays_persistent) {
+    m.persistent = 0;
+    m.net = m.stage;
+    const size_t words = (size_t)m.dilated_level_words * m.cascade;
+    m.lds_dilated_words = m.occ_dilated != nullptr && words * 4 <= (size_t)N_FRAGS * 64 * 16 ? (uint32_t)words : 0u;
+  }
+  return m;
+}
 int render_views_impl(nrf_context* c, int n_views, const float* cams, const float* poses, hipStream_t st, void* rgba, void* depth,
-                      size_t stride_px, int out_mode, int skip_outside, int* rows_out, const ProgressArgs* prog = nullptr) {
+                      size_t stride_px, int out_mode, int skip_outside, int* rows_out, const ProgressArgs* prog = nullptr,
+                      const RayArgs* rays = nullptr) {
   FrameParams P;
-  fill_frame_params(c, cams, poses, P);
+  static const float unit_cam[4] = {1.f, 1.f, 0.f, 0.f};
+  static const float unit_pose[16] = {1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 1.f};
+  fill_frame_params(c, rays ? unit_cam : cams, rays ? unit_pose : poses, P);
+  if (rays) P.fast_interp = 0;
+  const DevModel dm = rays ? rays_model(c) : c->dm;
   P.out_mode = out_mode;
   P.skip_outside = skip_outside;
   // one or two views alone are latency-bound, not throughput-bound: their last tiles end sooner when every ray queues its full
@@ -1379,11 +1407,11 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
   // the first round on, and every split group queues its own eight samples per ray behind a terminating one) -- small frames
   // keep the transmittance-dependent queue, which holds their evaluated samples within 15 % of the composited ones
   // (tests/test_parity_gpu.py, test_generic_gpu.py, test_golden.py; pixels cannot depend on it: tests/test_persistent_gpu.py)
-  const bool all_tail = (long long)c->n_local_tiles * n_views < (long long)c->dm.n_cus * std::max(1u, c->dm.persist_waves);
+  const bool all_tail = (long long)c->n_local_tiles * n_views < (long long)dm.n_cus * std::max(1u, dm.persist_waves);
   if (n_views <= 2 && !c->sample_cap_forced && !all_tail) P.sample_cap = 0;
   c->call_index = (c->call_index + 1) % CALL_RING;
   char* counters = call_slot(c, c->call_index);
-  unsigned* plan = (c->plan_max_pos > 0 && prog == nullptr) ? (unsigned*)((char*)c->d_plan + (size_t)c->call_index * PLAN_BYTES) : nullptr;
+  unsigned* plan = (c->plan_max_pos > 0 && prog == nullptr && rays == nullptr) ? (unsigned*)((char*)c->d_plan + (size_t)c->call_index * PLAN_BYTES) : nullptr;
   HIP_TRY(hipEventRecord(c->ev0, st));  // (render_ms covers the clearing of the call's counters and the planning of its queues)
   // views per launch: NRF_MAX_VIEWS, fewer when the frames are so large that the persistent kernel's 24-bit queue positions
   // (strip rows of all views x strips per row) would not hold the launch (8K frames: 64 views)
@@ -1398,7 +1426,17 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
     std::memset(&VB, 0, sizeof(VB));
     VB.n_views = n_views - first < per_launch ? n_views - first : per_launch;
     VB.view_stride_px = stride_px;
-    for (int v = 0; v < VB.n_views; ++v) {
+    for (int v = 0; rays && v < VB.n_views; ++v) {  // (R, org, cam stay zero: no RAYS instance reads them)
+      VB.v[v].roi[0] = VB.v[v].roi[1] = 0;
+      VB.v[v].roi[2] = c->W - 1;
+      VB.v[v].roi[3] = c->H - 1;
+    }
+    if (rays) {
+      P.rays_o = rays->o + 3 * (size_t)first * rays->per_view;
+      P.rays_d = rays->d + 3 * (size_t)first * rays->per_view;
+      P.rays_per_view = (unsigned)rays->per_view;
+    }
+    for (int v = 0; !rays && v < VB.n_views; ++v) {
       nerf_matrix_to_ngp(poses + 16 * (size_t)(first + v), c->desc.scale, VB.v[v].R, VB.v[v].org);
       for (int i = 0; i < 4; ++i) VB.v[v].cam[i] = cams[4 * (size_t)(first + v) + i];
       view_roi(VB.v[v].R, VB.v[v].org, VB.v[v].cam, c->dm.occ_box, c->W, c->H, VB.v[v].roi);
@@ -1424,7 +1462,7 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
       P.prog_flags = prog->flags + (size_t)first * P.tiles_y;
       P.prog_epoch = (int)prog->epoch;
     }
-    HIP_TRY(launch_render(c->dm, P, VB, rgba ? (char*)rgba + (size_t)first * stride_px * px_bytes_a : nullptr,
+    HIP_TRY(launch_render(dm, P, VB, rgba ? (char*)rgba + (size_t)first * stride_px * px_bytes_a : nullptr,
                           (char*)depth + (size_t)first * stride_px * px_bytes_b, counters, st, first == 0, plan,
                           (unsigned)c->plan_max_pos));
   }
@@ -1449,9 +1487,9 @@ int check_renderable(nrf_context* c, const float* cams, const float* poses, int 
 
 extern "C" {
 
-int nrf_render_views(nrf_context* c, int n_views, const float* cams, const float* poses, void* stream, nrf_frame* out) {
-  int rc = check_renderable(c, cams, poses, n_views);
-  if (rc) return rc;
+// nrf_render_views and nrf_render_rays behind their argument checks (rays == nullptr: cameras)
+static int render_frames(nrf_context* c, int n_views, const float* cams, const float* poses, const RayArgs* rays, void* stream, nrf_frame* out) {
+  int rc = NRF_OK;
   const bool bound = c->bound_rgba || c->bound_rgbd8 || c->bound_rgb8;
   if (!bound && n_views > c->max_views)
     return fail(NRF_E_STATE, "more views than the context's buffers hold: call nrf_set_max_views or nrf_bind_output");
@@ -1470,7 +1508,7 @@ int nrf_render_views(nrf_context* c, int n_views, const float* cams, const float
     depth = c->bound_depth8;
     mode = OUT_U8;
   }
-  rc = render_views_impl(c, n_views, cams, poses, st, rgba, depth, c->n_out_px, mode, 0, nullptr);
+  rc = render_views_impl(c, n_views, cams, poses, st, rgba, depth, c->n_out_px, mode, 0, nullptr, nullptr, rays);
   if (rc) return rc;
   const bool floats = mode == OUT_F32;
   c->last_rgba = floats ? rgba : nullptr;  // (an 8-bit frame in a bound buffer is the caller's to read)
@@ -1487,6 +1525,25 @@ int nrf_render_views(nrf_context* c, int n_views, const float* cams, const float
     out->view_stride_px = (int64_t)c->n_out_px;
   }
   return NRF_OK;
+}
+
+int nrf_render_views(nrf_context* c, int n_views, const float* cams, const float* poses, void* stream, nrf_frame* out) {
+  int rc = check_renderable(c, cams, poses, n_views);
+  if (rc) return rc;
+  return render_frames(c, n_views, cams, poses, nullptr, stream, out);
+}
+
+int nrf_render_rays(nrf_context* c, int n_views, const void* rays_o, const void* rays_d, uint64_t rays_per_view, void* stream,
+                    nrf_frame* out) {
+  static const float none[16] = {};  // (check_renderable's null test is for cameras)
+  int rc = check_renderable(c, none, none, n_views);
+  if (rc) return rc;
+  if (!rays_o || !rays_d) return fail(NRF_E_INVALID, "null argument");
+  if (rays_per_view < 1 || rays_per_view > (uint64_t)c->W * (uint64_t)c->H)
+    return fail(NRF_E_INVALID, "rays_per_view must be 1 .. width * height of nrf_set_resolution");
+  if (c->opt.perturb > 0) return fail(NRF_E_UNSUPPORTED, "nrf_render_rays has no perturb instances (nrf_options.perturb must be 0)");
+  const RayArgs rays{(const float*)rays_o, (const float*)rays_d, rays_per_view};
+  return render_frames(c, n_views, nullptr, nullptr, &rays, stream, out);
 }
 
 // ---- host frames: the reference's render_frame ends in HOST memory (R/src/nerf_render.cu:345-359: D2H of the float
@@ -1852,6 +1909,22 @@ extern "C" int nrf_debug_instance(nrf_context* c) {
   const int net = (int)c->dm.net;
   const int code = net == NET_HOT ? 0 : net == NET_GENERIC ? 1 : net == NET_WIDE ? 2 : net == NET_WIDE_SH ? 4 : net_grid_f(net) ? 5 : 3;
   return code + (c->dm.persistent ? 16 : 0);
+}
+
+// Diagnostic (not part of include/nerfhip.h): which RAYS instance nrf_render_rays launches for the loaded model -- the stage code of
+// nrf_debug_instance (0 register-resident, 1 generic, 2 wide), + 16 for the persistent form (the hot shape whose tables fit)
+extern "C" int nrf_debug_rays_instance(nrf_context* c) {
+  if (!c || !c->model_loaded) return -1;
+  if (c->rays_persistent) return 16;
+  const int st = (int)c->dm.stage;
+  return st == NET_GENERIC ? 1 : st == NET_WIDE ? 2 : 0;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the guard of caller-supplied rays (ray_valid, nrf_device.h) on the host -- the same
+// function the RAYS instances apply per ray; 1 = the ray is rendered, 0 = its pixel is the background
+extern "C" int nrf_debug_ray_valid(const float o[3], const float d[3]) {
+  if (!o || !d) return 0;
+  return ray_valid(o, d) ? 1 : 0;
 }
 
 // Diagnostic (not part of include/nerfhip.h): plan_model of a descriptor without a device, at an explicit quad-copy budget (MiB) --

@@ -222,7 +222,32 @@ struct FrameParams {
   // persistent kernel: the launch's queue order (plan_sort_kernel): entry [class offset + i] = the queue position the i-th pull of
   // that class renders -- a permutation of each class's positions, heaviest strips first.  nullptr: positions in order.
   const unsigned* plan_order;
+  // RAYS instances (nrf_render_rays): the caller's rays of the launch's view 0, fp32 [n_views][rays_per_view][3] each; pixel
+  // (px, py) of view v takes ray v * rays_per_view + py * W + px, a pixel whose ray number is >= rays_per_view has no ray.
+  // nullptr in every other launch (no other instance reads these fields).
+  const float* rays_o;
+  const float* rays_d;
+  unsigned rays_per_view;
 };
+
+// ------------------------------------------------------------- ray guard ----
+// The march of render_utils.h:593-653 never ends once t + dt == t in fp32: with dt_min = 0.0034 that is t ~ 2^24 dt ~ 5.7e4 (the
+// reference hangs there; so would these kernels).  A pinhole view is kept away from it on the host, by its camera position
+// (render_views_impl); caller-supplied rays are kept away from it per ray, in the kernel, by ray_valid below.
+constexpr float MAX_CAMERA_DISTANCE = 4096.0f;  // in the reference's ngp units (0.33 x the nerf pose's + 0.5)
+// |d|^2 of a caller-supplied ray.  Not a unit-length check: it bounds t.  A ray leaves the aabb (half-diagonal sqrt(3) * bound)
+// after a path of at most |o| + sqrt(3) * bound <= 4096 + sqrt(3) * bound ... measured in t that is the path over |d| >= 0.5, so
+// far <= 2 * (4096 + 2 sqrt(3) * bound) (entry to exit: one diagonal more) -- 8.2e3 + 7 * bound, well short of 5.7e4 for any bound
+// a model loads with; the upper bound keeps dt (in t) from shrinking below dt_min / 2 in path length.
+constexpr float RAY_DIR_NORM2_MIN = 0.25f, RAY_DIR_NORM2_MAX = 4.0f;
+// A caller-supplied ray is rendered only if every component is finite, |o| <= MAX_CAMERA_DISTANCE and |d|^2 lies in
+// [RAY_DIR_NORM2_MIN, RAY_DIR_NORM2_MAX]; any other ray's pixel is the background.  Zero components of d are legal (the slab tests'
+// nan branch).  (NaN fails every comparison; an infinite component makes the norm infinite or NaN.)
+__host__ __device__ inline bool ray_valid(const float o[3], const float d[3]) {
+  const float o2 = o[0] * o[0] + (o[1] * o[1] + o[2] * o[2]);
+  const float d2 = d[0] * d[0] + (d[1] * d[1] + d[2] * d[2]);
+  return o2 <= MAX_CAMERA_DISTANCE * MAX_CAMERA_DISTANCE && d2 >= RAY_DIR_NORM2_MIN && d2 <= RAY_DIR_NORM2_MAX;
+}
 
 // ------------------------------------------------------------------ misc ----
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }

@@ -767,6 +767,12 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
   const int blocks = VB.blocks_per_view * VB.n_views;
   const bool perturb = P.perturb != 0;  // (render_kernel's PERTURB instances: per-strip workgroups, tables in global memory)
   const bool lds_tab = M.lds_coarse_words > 0 && !perturb;
+  // caller-supplied rays (nrf_render_rays): the RAYS instances (nrf_kernels_rays.hip) -- the persistent one exists for the hot shape
+  // only (the caller passes M.persistent == 0 for every other model: nrf_api.hip rays_model); there is no camera to price strips
+  // from, so the queues hand out their positions in order
+  const bool rays = P.rays_o != nullptr;
+  if (rays && (perturb || P.rays_d == nullptr || (M.persistent && M.net != NET_HOT))) return hipErrorInvalidValue;
+  if (rays) plan = nullptr;
   if (M.persistent && lds_tab) {
     // work queues: per view the strip rows its region of interest touches (sharded: the local strips of those rows)
     const int strips_x = (P.tiles_x + 3) >> 2, N = P.shard_count, idx = P.shard_index;
@@ -819,7 +825,8 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     const int form = march_form(M.H, M.cascade, M.bound);
     const bool unit = form == MARCH_FORM_UNIT, pow2 = form == MARCH_FORM_POW2;
     const PersistLaunch L{&M, &P, &VB, rgba, depth, counters, queue, st, lds, wgs, waves, unit, pow2};
-    if (M.net == NET_HOT) e = launch_persistent_hot(L);                          // the base.json shape (nrf_kernels_hot.hip)
+    if (rays) e = launch_persistent_rays(L);
+    else if (M.net == NET_HOT) e = launch_persistent_hot(L);                          // the base.json shape (nrf_kernels_hot.hip)
     else if (M.net == NET_GENERIC) e = launch_persistent_generic(L);             // nrf_kernels_generic.hip
     else if (M.net == NET_WIDE || M.net == NET_WIDE_SH) e = launch_persistent_wide(L);  // Frequency / SH directions beyond 16 values (nrf_kernels_wide.hip)
     else if (net_grid_f((int)M.net)) e = launch_persistent_grid(L);             // other grids in front of base.json's MLPs (nrf_kernels_grid.hip)
@@ -839,7 +846,8 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
   // mip_bound == 1 (MARCH_UNIT) or several cascades and a power-of-two bound (MARCH_POW2)
   const int form = march_form(M.H, M.cascade, M.bound);
   const bool unit = lds_tab && form == MARCH_FORM_UNIT, pow2 = lds_tab && form == MARCH_FORM_POW2;
-  const hipError_t es = launch_strip(StripLaunch{&M, &P, &VB, rgba, depth, counters, st, lds, blocks, lds_tab, unit, pow2, perturb});
+  const StripLaunch SL{&M, &P, &VB, rgba, depth, counters, st, lds, blocks, lds_tab, unit, pow2, perturb};
+  const hipError_t es = rays ? launch_strip_rays(SL) : launch_strip(SL);
   if (es != hipSuccess) return es;
   return hipGetLastError();
 }
@@ -1063,6 +1071,7 @@ void preload_kernels(bool all) {
     preload_generic();
     preload_strip();
     preload_grid();
+    preload_rays();
   }
 }
 

@@ -674,13 +674,18 @@ __device__ __forceinline__ uint32_t ray_number(const FrameParams& P, uint32_t pi
 // PERTURB: the march's perturb branch (render_utils.h:585-589; nrf_options.perturb > 0).  Dead in the reference (m_perturb = false,
 // no setter), so it lives in instances of its own -- render_kernel<.., PERTURB = true>, nrf_kernels_strip.hip -- and costs the
 // product path no register: several persistent instances sit at their register limit.
-template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false>
+// RAYS (nrf_render_rays): every lane has an origin of its own.  Three more registers alive through the network phase do not fit
+// the hot persistent instance (128 VGPR + AGPR at 16 waves), so a live lane re-reads its origin at the top of every round's march --
+// the only phase that uses it -- from the origins of view rays_view (FrameParams::rays_o; 12 bytes per ray and round against ~512 per sample, L2-resident)
+// by the ray number its pix_idx stands for: o_in is ignored, and a ray handed to a helper wave needs no origin in its mail.
+template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false, bool RAYS = false>
 __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams& P, const MarchConst& mc, const LdsMap& lm,
-                                            const uint32_t* coarse_lds, const float* ctab_lds, int lane, const float (&o)[3],
+                                            const uint32_t* coarse_lds, const float* ctab_lds, int lane, const float (&o_in)[3],
                                             const float (&d)[3], float rdx, float rdy, float rdz, int sx, int sy, int sz,
                                             float far_m, float t_skip, float t, float tc, bool alive, TileAcc& acc,
                                             TileStats& ts, int n_ray_samples = 0, const HelpArgs* ha = nullptr, uint32_t pix_idx = 0u,
-                                            float near = 0.f, float far = 0.f, bool* given_out = nullptr) {
+                                            float near = 0.f, float far = 0.f, bool* given_out = nullptr,
+                                            int rays_view = 0) {
   const uint4* wl = lm.wl;
   const LevelParams* lvs = lm.lvs;
   WaveLds* W = lm.W;
@@ -742,6 +747,19 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
     // A ray whose transmittance is already low will probably terminate within the next samples: whatever it queues behind its
     // terminating sample is evaluated for nothing (the reference's own schedule wastes 8.6 % that way, an unconditional queue
     // of 8 here 2.4 %).  The per-round queue shrinks with T; per-ray semantics -- and so every pixel -- do not depend on it.
+    float o[3] = {o_in[0], o_in[1], o_in[2]};
+    if constexpr (RAYS) {  // (a value of this round alone: nothing of it is carried from round to round)
+      o[0] = o[1] = o[2] = 0.f;
+      if (alive) {
+        uint32_t pi = pix_idx;
+        asm volatile("" : "+v"(pi));  // (this round's ray number and load: hoisted out of the loop they would live in registers -- or scratch -- again)
+        const uint32_t off = 3u * ray_number(P, pi);
+        const float* ov = P.rays_o + 3 * (size_t)rays_view * P.rays_per_view;  // (wave-uniform)
+        o[0] = ov[off];
+        o[1] = ov[off + 1u];
+        o[2] = ov[off + 2u];
+      }
+    }
     const float Tq = 1.0f - ws;
     int cap = 8;
     if (P.sample_cap == 1) cap = Tq < 0.02f ? 1 : (Tq < 0.1f ? 2 : (Tq < 0.4f ? 4 : 8));
@@ -854,12 +872,34 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
 #endif
 }
 
+// RAYS instances: the ray of pixel number rn (py * W + px) of view `view` from the caller's arrays (FrameParams::rays_o / rays_d) in
+// place of ray generation.  False -- and a harmless ray -- for a pixel without a ray (outside the frame, rn >= rays_per_view) and for
+// a ray the guard refuses (ray_valid, nrf_device.h): the caller makes such a pixel the background.
+__device__ __forceinline__ bool load_ray(const FrameParams& P, int view, uint32_t rn, bool in_img, float (&o)[3], float (&d)[3]) {
+  bool ok = in_img && rn < P.rays_per_view;
+  o[0] = o[1] = o[2] = 0.f;
+  d[0] = d[1] = 0.f;
+  d[2] = 1.f;
+  if (ok) {
+    const size_t i = 3 * ((size_t)view * P.rays_per_view + rn);
+    const float ro[3] = {P.rays_o[i], P.rays_o[i + 1], P.rays_o[i + 2]};
+    const float rd[3] = {P.rays_d[i], P.rays_d[i + 1], P.rays_d[i + 2]};
+    ok = ray_valid(ro, rd);
+    if (ok) {
+      o[0] = ro[0]; o[1] = ro[1]; o[2] = ro[2];
+      d[0] = rd[0]; d[1] = rd[1]; d[2] = rd[2];
+    }
+  }
+  return ok;
+}
+
 // ------------------------------------------------------- the render kernel ----
 // 256 threads, >= 4 waves per SIMD (four workgroups per CU, 39.9 KB of LDS each): caps the kernel at
 // 128 VGPRs.  Small workgroups matter: a workgroup's LDS and wave slots are only released when its
 // slowest tile is done.
 // (the generic instance is bound by its LDS rows, not by registers: no 128-VGPR cap there)
-template <int NET, bool COARSE_LDS, int MARCH, bool PERTURB = false>
+// RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray) -- instances of their own, nrf_kernels_rays.hip
+template <int NET, bool COARSE_LDS, int MARCH, bool PERTURB = false, bool RAYS = false>
 __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NET_WIDE ? 3 : 4)) void render_kernel(const DevModel M, const FrameParams P, const ViewBatch VB,
                                                      float4* __restrict__ rgba, float* __restrict__ depth,
                                                      unsigned long long* __restrict__ counters) {
@@ -933,11 +973,14 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   }
 #endif
   // ---- ray generation + aabb
-  const float o[3] = {V.org[0], V.org[1], V.org[2]};
+  float o[3] = {V.org[0], V.org[1], V.org[2]};
   float d[3];
-  ray_dir(V.R, V.cam, px, py, d);
+  bool has_ray = true;
+  if constexpr (RAYS) has_ray = load_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, in_img, o, d);
+  else ray_dir(V.R, V.cam, px, py, d);
   float near, far;
   near_far(M.aabb, o, d, P.min_near, near, far);
+  if constexpr (RAYS) if (!has_ray) near = far = 3.402823466e+38f;  // (what near_far gives a ray that misses the aabb)
   const float rdx = 1 / d[0], rdy = 1 / d[1], rdz = 1 / d[2];
   const MarchConst mc = march_const(M, P.dt_gamma);
   const int sx = __builtin_signbitf(d[0]) ? 0 : 1;  // copysignf(1, d) > 0: the far face of the cell
@@ -1063,8 +1106,9 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   TileStats ts;
   // (pix_idx as in the persistent kernel: what ray_number reads for the perturb branch)
   const uint32_t pix_idx = P.tile_major ? (uint32_t)k_local * 64u + (uint32_t)lane : (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
-  tile_rounds<NET, COARSE_LDS, MARCH, false, false, PERTURB>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m,
-                                                             t_skip, t, tc, alive, acc, ts, 0, nullptr, pix_idx);
+  tile_rounds<NET, COARSE_LDS, MARCH, false, false, PERTURB, RAYS>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz,
+                                                                   far_m, t_skip, t, tc, alive, acc, ts, 0, nullptr, pix_idx, 0.f, 0.f, nullptr,
+                                                                   view);
   const float ws = acc.ws, dep = acc.dep, cr = acc.cr, cg = acc.cg, cb = acc.cb;
   const unsigned n_samples = ts.n_samples, n_rounds = ts.n_rounds, n_tile_slots = ts.n_tile_slots;
   const unsigned n_composited = ts.n_composited;
@@ -1196,7 +1240,9 @@ static_assert(offsetof(PersistArgs, P) == (sizeof(DevModel) + alignof(FrameParam
 // U8: the instance that writes the reference's 8-bit Image layout (OUT_U8, store_tile_u8)
 // FAST: nrf_options::fast_interp (opt-in single-rounding interpolation; register-resident instance only) -- instances of
 // their own, so that the shipped default symbols keep the bit-exact arithmetic (tests/test_abi_cpu.py checks their ISA)
-template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, bool FAST = false>
+// RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray; every view's region of interest is its whole frame) --
+// instances of their own, nrf_kernels_rays.hip.  (FAST stays the last argument: tests/test_abi_cpu.py reads it off the symbol names)
+template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, bool RAYS = false, bool FAST = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const DevModel M0, const FrameParams P0, const ViewBatch VB0,
                                                                               float4* __restrict__ rgba0, float* __restrict__ depth0,
                                                                               unsigned long long* __restrict__ counters,
@@ -1367,11 +1413,14 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const unsigned samples_before = ts.n_samples;
 #endif
     // ---- ray generation + aabb (as render_kernel)
-    const float o[3] = {V.org[0], V.org[1], V.org[2]};
+    float o[3] = {V.org[0], V.org[1], V.org[2]};
     float d[3];
-    ray_dir(V.R, V.cam, px, py, d);
+    bool has_ray = true;
+    if constexpr (RAYS) has_ray = load_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, in_img, o, d);
+    else ray_dir(V.R, V.cam, px, py, d);
     float near, far;
     near_far(M.aabb, o, d, P.min_near, near, far);
+    if constexpr (RAYS) if (!has_ray) near = far = 3.402823466e+38f;
     const float rdx = 1 / d[0], rdy = 1 / d[1], rdz = 1 / d[2];
     const int sx = __builtin_signbitf(d[0]) ? 0 : 1;
     const int sy = __builtin_signbitf(d[1]) ? 0 : 1;
@@ -1432,8 +1481,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
       wave_sync();
       NRF_STAMP(t_setup_done);
       const HelpArgs ha = {hl, lm.W - wave, view};
-      tile_rounds<NET, true, MARCH, true, FAST>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m, t_skip, t, tc,
-                                                    alive, acc, ts, 0, &ha, pix_idx, near, far, &given);
+      tile_rounds<NET, true, MARCH, true, FAST, false, RAYS>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m, t_skip,
+                                                             t, tc, alive, acc, ts, 0, &ha, pix_idx, near, far, &given,
+                                                             view);
 #ifdef NRF_PHASE_TIMING
       if (lane == 0) {
         NRF_STAMP(t_end);
@@ -1552,8 +1602,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     bool given = false;
     const HelpArgs ha = {hl, lm.W - wave, view};
     // (t_skip: the occupancy lookups it would skip are of cells known to be empty -- looking them up changes nothing)
-    tile_rounds<NET, true, MARCH, true, FAST>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m, -3.402823466e+38f, t, tc,
-                                                  mine, acc, ts, n_ray_samples, &ha, pix_idx, near, far, &given);
+    // (RAYS: a helped ray's origin is re-read by its number -- pix_idx -- like every other ray's, tile_rounds)
+    tile_rounds<NET, true, MARCH, true, FAST, false, RAYS>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m,
+                                                           -3.402823466e+38f, t, tc, mine, acc, ts, n_ray_samples, &ha, pix_idx, near, far, &given,
+                                                           view);
     const OutPlanes op = view_planes<OUT8>(P, rgba0, depth0, view, VB.view_stride_px);
     const bool store = mine && !given;
     if (store) {  // get_image_and_depth, as in the tile loop
@@ -1638,6 +1690,7 @@ hipError_t launch_persistent_width(const PersistLaunch& L);
 hipError_t launch_persistent_wide(const PersistLaunch& L);
 hipError_t launch_persistent_generic(const PersistLaunch& L);
 hipError_t launch_persistent_grid(const PersistLaunch& L);
+hipError_t launch_persistent_rays(const PersistLaunch& L);  // FrameParams::rays_o != nullptr, NET_HOT (nrf_kernels_rays.hip)
 struct StripLaunch {
   const DevModel* M;
   const FrameParams* P;
@@ -1649,20 +1702,22 @@ struct StripLaunch {
   bool perturb;  // nrf_options.perturb > 0: the PERTURB instances (tables in global memory, generic march)
 };
 hipError_t launch_strip(const StripLaunch& L);
+hipError_t launch_strip_rays(const StripLaunch& L);  // FrameParams::rays_o != nullptr (nrf_kernels_rays.hip)
 void preload_hot();
 void preload_width();
 void preload_wide();
 void preload_generic();
 void preload_strip();
 void preload_grid();
+void preload_rays();
 
 // one instance of the persistent form: WV waves per workgroup, WL = generic weights in LDS, 8-bit output / fast_interp chosen at run time
 #define NRF_LAUNCH_PERSISTENT_F(G, U, WV, WL, O8, FI)                                                                    \
   do {                                                                                                                   \
     if (L.waves != (WV)) return hipErrorInvalidConfiguration; /* the host sized the workgroup's LDS for another instance */ \
-    hipError_t e_ = allow_lds(render_persistent_kernel<G, U, WV, WL, O8, FI>, L.lds);                                    \
+    hipError_t e_ = allow_lds(render_persistent_kernel<G, U, WV, WL, O8, false, FI>, L.lds);                                    \
     if (e_ != hipSuccess) return e_;                                                                                     \
-    hipLaunchKernelGGL((render_persistent_kernel<G, U, WV, WL, O8, FI>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, *L.M,  \
+    hipLaunchKernelGGL((render_persistent_kernel<G, U, WV, WL, O8, false, FI>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, *L.M,  \
                        *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue);         \
   } while (0)
 #define NRF_LAUNCH_PERSISTENT_W(G, U, WV, WL)                                                                            \

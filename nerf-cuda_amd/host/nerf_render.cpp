@@ -538,6 +538,17 @@ void NerfRender::generate_rays(Camera cam, Matrix4f pos, int threadid) {
   check(nrf_generate_rays_host(m_ctx[0], c4, pos.m, m_rays_o.data(), m_rays_d.data(), nullptr, nullptr), "nrf_generate_rays_host");
 }
 
+Image NerfRender::render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view) {
+  if (!m_have_network) throw std::runtime_error{"render_rays: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"render_rays: single-device renderers only (device groups do not take rays)"};
+  check(nrf_render_rays(m_ctx[0], 1, rays_o, rays_d, rays_per_view, nullptr, nullptr), "nrf_render_rays");
+  const size_t n = (size_t)resolution[0] * resolution[1];
+  m_rays_rgb.resize(3 * n);
+  m_rays_depth.resize(n);
+  check(nrf_read_u8(m_ctx[0], m_rays_rgb.data(), m_rays_depth.data()), "nrf_read_u8");
+  return Image(resolution[0], resolution[1], m_rays_rgb.data(), m_rays_depth.data());
+}
+
 void NerfRender::generate_density_grid() {
   // reference nerf_render.cu:388-429 (dead there: the density query is commented out at :415); completed behind
   // nrf_generate_density_grid with the reference's constants: decay 0.95 (:392), start value 1/64 (:393), scale

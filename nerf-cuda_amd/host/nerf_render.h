@@ -73,6 +73,11 @@ class NerfRender {
   float last_wait_render_ms() const { return m_last_wait_render_ms; }  // device time of the batch wait_frames returned last
   // device ray buffers of the reference are internal to the fused kernel; this fills host copies
   void generate_rays(Camera cam, Matrix4f pos, int threadid);
+  // Frame from caller-supplied rays (addition; nrf_render_rays): rays_o / rays_d are DEVICE pointers, fp32 [rays_per_view][3] in the
+  // space and layout generate_rays produces (ngp units, row-major pixels of the set_resolution frame); pixels beyond
+  // rays_per_view and rays the guard refuses are background.  Single-device renderers only (device groups are out of its
+  // scope).  The Image is host memory of this object, valid until the next render_rays.
+  Image render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view);
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in
   // nrf_generate_density_grid); reload_network_from_file calls it for a snapshot that carries no density grid
   void generate_density_grid();
@@ -106,6 +111,7 @@ class NerfRender {
   Vector2i resolution;
   float m_last_wait_render_ms = 0.f;
   std::vector<float> m_rays_o, m_rays_d;
+  std::vector<unsigned char> m_rays_rgb, m_rays_depth;  // render_rays' Image
 };
 
 // Camera path from a NeRF-synthetic / instant-ngp `transforms.json` (intrinsics scaled to width x height; 0 = the file's w / h)

@@ -23,7 +23,7 @@ import numpy as np
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libnerfhip.so"
 
-NRF_ABI_VERSION = 6
+NRF_ABI_VERSION = 7
 GATHER_PEER_COPY, GATHER_RCCL = 0, 1  # nrf_group_set_gather
 NRF_MAX_VIEWS = 128
 NRF_OK, NRF_E_INVALID, NRF_E_UNSUPPORTED, NRF_E_NODEVICE, NRF_E_HIP, NRF_E_STATE, NRF_E_PARAMS = range(7)
@@ -174,6 +174,7 @@ _SIGS = {
                                    C.POINTER(Frame)]),
     "nrf_render_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
                                    C.POINTER(Frame)]),
+    "nrf_render_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Frame)]),
     "nrf_read_view_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nrf_read_view_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nrf_bind_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -631,6 +632,14 @@ class NerfHip:
             raise ValueError("cams and poses must have the same length")
         f = Frame()
         _check(self.lib.nrf_render_views(self.h, len(cams), _fptr(cams), _fptr(poses), C.c_void_p(stream or 0), C.byref(f)))
+        return f
+
+    def render_rays(self, rays_o_ptr, rays_d_ptr, rays_per_view: int, n_views: int = 1, stream=None) -> Frame:
+        """nrf_render_rays: frames from caller-supplied rays -- device fp32 [n_views][rays_per_view][3] origins and directions
+        (ngp units, row-major pixels, as generate_rays writes them); pixels beyond rays_per_view and guarded rays are background."""
+        f = Frame()
+        _check(self.lib.nrf_render_rays(self.h, int(n_views), C.c_void_p(rays_o_ptr or 0), C.c_void_p(rays_d_ptr or 0),
+                                        int(rays_per_view), C.c_void_p(stream or 0), C.byref(f)))
         return f
 
     def read_view_f32(self, view: int):

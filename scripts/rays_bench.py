@@ -1,0 +1,109 @@
+"""What rendering from caller-supplied rays costs against the pinhole path, on the flagship workload: the 1080p, T = 2^19
+base.json-shaped model in 16-view launches.  One process alternates three legs, so that all of them see the same box and clock:
+
+  views          nrf_render_views of 16 orbit cameras (code nrf_render_rays does not touch: the baseline)
+  rays           nrf_render_rays on the nrf_generate_rays output of the same cameras, persistent RAYS instance
+  rays_strip     the same through the per-strip RAYS instance (a context created under NRF_PERSISTENT=0)
+
+Per leg: device ms per view (hipEvents around the call's launches, nrf_stats.render_ms) -- median, minimum, maximum over the
+repetitions --, samples, and the shader clock the persistent kernel measured in its launches (0: the per-strip kernel has no such
+stamp).  The frames of the three legs are compared bit for bit first.  Prints one JSON object.
+
+Run it under a time limit:   timeout -k 10 300 python3 scripts/rays_bench.py [--reps 7] [--out profiles/.../rays_bench.json]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "nerf-cuda_amd"), os.path.join(ROOT, "tests")]
+import numpy as np, torch  # noqa: E402
+import models, nerfhip as nh, synthetic as syn  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--views", type=int, default=16)
+ap.add_argument("--width", type=int, default=1920)
+ap.add_argument("--height", type=int, default=1080)
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+W, H, V = args.width, args.height, args.views
+cams = np.stack([syn.default_camera(W, H)] * V)
+poses = np.stack([syn.orbit_pose(360.0 * i / V, 30.0) for i in range(V)])
+desc, keep, _ = models.build_model(log2_hashmap_size=19, H=128)
+
+
+def context(persistent):
+    os.environ["NRF_PERSISTENT"] = persistent
+    try:
+        c = nh.NerfHip(0)
+    finally:
+        os.environ.pop("NRF_PERSISTENT", None)
+    c.load_model(desc)
+    c.set_resolution(W, H)
+    c.set_max_views(V)
+    return c
+
+
+cp, cs = context("1"), context("0")
+rays_o = torch.empty((V, W * H, 3), device="cuda")
+rays_d = torch.empty((V, W * H, 3), device="cuda")
+torch.cuda.synchronize()
+for v in range(V):
+    cp.generate_rays(cams[v], poses[v], rays_o[v].data_ptr(), rays_d[v].data_ptr(), 0, 0)
+import ctypes as C  # noqa: E402
+inst = cp.lib.nrf_debug_rays_instance
+inst.restype, inst.argtypes = C.c_int, [C.c_void_p]
+assert inst(cp.h) == 16 and inst(cs.h) == 0, (inst(cp.h), inst(cs.h))
+
+LEGS = {
+    "views": lambda: cp.render_views(cams, poses),
+    "rays": lambda: cp.render_rays(rays_o.data_ptr(), rays_d.data_ptr(), W * H, n_views=V),
+    "rays_strip": lambda: cs.render_rays(rays_o.data_ptr(), rays_d.data_ptr(), W * H, n_views=V),
+}
+CTX = {"views": cp, "rays": cp, "rays_strip": cs}
+
+# the three legs render the same frames
+frames = {}
+for name, run in LEGS.items():
+    run()
+    frames[name] = [CTX[name].read_view_f32(v) for v in (0, V // 2, V - 1)]
+for name in ("rays", "rays_strip"):
+    for a, b in zip(frames[name], frames["views"]):
+        assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), name
+del frames
+
+ms = {k: [] for k in LEGS}
+clock = {k: [] for k in LEGS}
+samples = {}
+for _ in range(args.reps):
+    for name, run in LEGS.items():
+        run()
+        st = CTX[name].stats()
+        ms[name].append(st.render_ms / V)
+        clock[name].append(st.shader_clock_mhz)
+        samples[name] = int(st.n_samples)
+res = {"workload": f"{V} views of {W}x{H}, T = 2^19 base.json shape", "reps": args.reps, "legs": {}}
+for name in LEGS:
+    a = np.array(ms[name])
+    res["legs"][name] = {"ms_per_view_median": round(float(np.median(a)), 4), "ms_per_view_min": round(float(a.min()), 4),
+                         "ms_per_view_max": round(float(a.max()), 4), "n_samples": samples[name],
+                         "shader_clock_mhz": round(float(np.median(clock[name])), 1),
+                         "ms_per_view_all": [round(float(x), 4) for x in a]}
+    print(f"{name:11s} {np.median(a):7.4f} ms/view (min {a.min():.4f}, max {a.max():.4f})  samples {samples[name]}  "
+          f"shader_clock_mhz {np.median(clock[name]):.0f}", file=sys.stderr, flush=True)
+m = {k: res["legs"][k]["ms_per_view_median"] for k in LEGS}
+spread = (res["legs"]["views"]["ms_per_view_max"] - res["legs"]["views"]["ms_per_view_min"]) / m["views"]
+res["rays_over_views"] = round(m["rays"] / m["views"], 4)
+res["rays_strip_over_rays"] = round(m["rays_strip"] / m["rays"], 4)
+res["views_run_to_run_spread"] = round(spread, 4)  # (max - min) / median of the baseline leg
+q1, q3 = np.percentile(np.array(ms["views"]), [25, 75])
+res["views_interquartile_spread"] = round(float((q3 - q1) / m["views"]), 4)
+print(json.dumps(res))
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+cp.close()
+cs.close()
