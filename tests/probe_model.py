@@ -14,7 +14,8 @@ A probe model is any model `models.build_model` makes with its MLP parameters an
 So for every ray that meets occupied space: pixel rgb == the fp16 value of the chosen features at the ray's first march
 sample, bit for bit, and alpha == 1.  Hidden activation ReLU (rgb = relu(s v)) or None (rgb = s v); rgb output None.
 
-LEGS lists what the GPU file renders and the CPU file proves its conditions for."""
+LEGS lists what the GPU file renders and the CPU file proves its conditions for.  FOG_LEGS (at the end): the same models with a
+thin density, whose frames show the compositor (test_fog_cpu.py, test_fog_gpu.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -68,9 +69,10 @@ def resolve(build_kw):
     return kw
 
 
-def probe_desc(build_kw, routes, density_grid=None, seed=0):
+def probe_desc(build_kw, routes, density_grid=None, seed=0, sigma_weight=11.0):
     """routes: three of ("grid", feature index, sign) / ("dir", value index, sign), one per colour channel.
-    density_grid: None (the synthetic object) or "random" (random_density_grid).  Returns (desc, keep, info)."""
+    density_grid: None (the synthetic object) or "random" (random_density_grid).  sigma_weight: the weight of the constant-1
+    feature's route to g[0] (11: every ray ends at its first sample; 1 .. 4.5: a fog, see FOG_LEGS).  Returns (desc, keep, info)."""
     assert len(routes) == 3
     desc, keep, cfg = _build(build_kw)
     feat_raw, feat_w, width, dens_hidden, rgb_hidden, dir_raw, dir_w = shape = syn.network_shape(cfg)
@@ -99,7 +101,7 @@ def probe_desc(build_kw, routes, density_grid=None, seed=0):
             m[out, col] = (first if i == 0 else 1.0) * (last if i == len(mats) - 1 else 1.0)
             col = out
 
-    chain(D, d_neurons, 0, sigma_feature, 0, 1.0, last=11.0)
+    chain(D, d_neurons, 0, sigma_feature, 0, 1.0, last=float(sigma_weight))
     for c, (kind, k, sign) in enumerate(routes):
         assert sign in (1, -1)
         if kind == "grid":
@@ -127,7 +129,7 @@ def probe_desc(build_kw, routes, density_grid=None, seed=0):
         assert density_grid is None
     desc2, keep2 = nh.desc_from_config(cfg, params, grid)
     info = dict(routes=list(routes), bound=float(desc2.bound), act=act, sigma_feature=sigma_feature, shape=shape, F=F,
-                n_levels=int(desc2.n_levels), frequency=cfg["dir_encoding"]["nested"][0]["otype"] == "Frequency",
+                n_levels=int(desc2.n_levels), sigma_weight=float(sigma_weight), frequency=cfg["dir_encoding"]["nested"][0]["otype"] == "Frequency",
                 sh=sh, dir_pad=dir_pad)
     return desc2, keep2, info
 
@@ -285,3 +287,127 @@ def leg_models(leg):
     """(desc, keep, info) of every model of a leg, one per three routes."""
     for i, routes in enumerate(leg["routes"]):
         yield probe_desc(leg["build_kw"], routes, leg["density_grid"], seed=1000 + i)
+
+
+# --------------------------------------------------------------------------- fog legs
+# A fog probe model: a sigma_weight of FOG_WEIGHTS in place of 11 -- sigma = fp16(exp(weight * ~1)) ~ 2.6 / 8.1 / 22 / 79 at every
+# sample, still an exact fp16 value, the same bits in kernel and oracle; rays now run through many samples and end with alphas
+# spread over (0, 1): the frame shows the compositor.  tests/fog_reference.py restates it in float64 with a derived bound;
+# test_fog_cpu.py proves every condition below for every leg, test_fog_gpu.py holds the kernels to the bound.
+#
+# Every leg renders two models of the same routes and weight, one frame each:
+#   the synthetic object from the camera inside the volume -- every ray hits, 100+ samples per ray, which leave the volume with
+#     alpha < 1 in a thin fog and stop on the transmittance test in a thick one;
+#   random_density_grid from an orbit pose -- short rays through scattered cells, final alphas all over (0, 1), rays that miss.
+# (One grid alone cannot give a thick fog both: at sigma 90 the object is opaque but for chords of half a cell, and the
+# scattered cells are too few for T to reach 1e-4.)  The strength legs render both poses with both grids.
+# The weights are "about 1, 2, 3 and 4.5", moved to the nearest values for which exp(g0) of every g0 = fp16(weight * v), v within
+# a few fp16 ulps of 1 (the interpolated constant wobbles), stays 3 * 2^-16 relative away from an fp16 rounding boundary: at
+# 1, 3 and 4.5 themselves one of the sigmas sits within 2^-16 of a tie, where v_exp_f32 and libm may round apart
+# (test_fog_cpu.py checks the values each leg really meets).  sigma ~ 2.6, 8.1, 21.9, 79.
+FOG_WEIGHTS = W1, W2, W3, W4 = (0.96875, 2.09375, 3.0859375, 4.375)
+FOG_FRAMES = ((None, 1), ("random", 0))  # (density grid, index into poses())
+FOG_SWITCHES = {
+    "cap0": {"NRF_SAMPLE_CAP": "0"}, "cap1": {"NRF_SAMPLE_CAP": "1"}, "cap2": {"NRF_SAMPLE_CAP": "2"},
+    "tailsplit0": {"NRF_TAIL_SPLIT": "0"}, "marchff0": {"NRF_MARCH_FF": "0"}, "budget3": {"NRF_MARCH_BUDGET": "3"},
+}
+# name -> (nrf_options fields, sigma weight).  max_steps: around the 8-sample round and not a multiple of it; weight W2: a ray cut
+# after 1 .. 37 samples ends with alpha 0.02 .. 0.9
+FOG_OPTIONS = {
+    "max_steps1": (dict(max_steps=1), W2), "max_steps7": (dict(max_steps=7), W2), "max_steps8": (dict(max_steps=8), W2),
+    "max_steps9": (dict(max_steps=9), W2), "max_steps37": (dict(max_steps=37), W2),
+    "density_scale0.37": (dict(density_scale=0.37), W4), "density_scale2": (dict(density_scale=2.0), W3),
+    "bg0": (dict(bg_color=0.0), W2), "bg0.25": (dict(bg_color=0.25), W3),
+    "min_near0.05": (dict(min_near=0.05), W3),
+    "dt_gamma0": (dict(dt_gamma=0.0), W3), "dt_gamma1_32": (dict(dt_gamma=1.0 / 32.0), W2),
+    "perturb5": (dict(perturb=5), W3),
+}
+FOG_LARGE = (333, 211)  # several strips per queue, and a tail that is split: a 64 x 48 frame is all tail
+
+
+def fog_routes(L, F, dir_raw, n, frequency):
+    """Two features of different fine levels (the upper half: their values change from sample to sample along a ray, so a
+    sample left out moves the pixel), in both signs, and a third route: a coarse level, or in every other leg the last
+    direction value (constant along a ray: the channel shows the weights alone).  No direction route where the encoding is
+    Frequency (v_sin_f32 against sinf: not exact, see test_probe_gpu.py)."""
+    half = L // 2
+
+    def level(j):
+        return half + (n + j) % (L - half)
+    third = ("dir", dir_raw - 1, 1) if n % 2 and not frequency else ("grid", (n % half) * F, 1)
+    return [("grid", level(0) * F + n % F, 1), ("grid", level(3) * F + (n + 1) % F, -1), third]
+
+
+def _fog_leg(family, name, iname, sched, gather, weight, n, frames=FOG_FRAMES, geometry=None, opts_kw=None, option=None, env=None,
+             same_as_plain=False, size=(FRAME_W, FRAME_H)):
+    kw, own, stage, ienv = INSTANCES[iname]
+    kw = dict(kw, **(GEOMETRIES[geometry] if geometry else {}))
+    feat_raw, _, _, _, _, dir_raw, _ = syn.network_shape(syn.base_config(**INSTANCES[iname][0]))
+    F = kw.get("n_features_per_level", 2)
+    routes = fog_routes(feat_raw // F, F, dir_raw, n, kw.get("dir_otype") == "Frequency")
+    genv, budget, addresses = dict(GATHER, **NO_GATHER_AXIS)[gather]
+    sched_env = PERSISTENT if sched == "persistent" else STRIP
+    return dict(id=f"fog-{family}-{name}", family=family, instance=iname, sched=sched, gather=gather, build_kw=dict(T12, **kw),
+                own=own, stage=stage, env=dict(ienv, **sched_env, **genv, **(env or {})), plain_env=dict(ienv, **sched_env, **genv),
+                budget_mb=budget, addresses=addresses if geometry is None else None, routes=routes,
+                weight=float(weight), frames=tuple(frames), opts_kw=dict(opts_kw or {}), option=option, same_as_plain=same_as_plain,
+                size=tuple(size))
+
+
+def _fog_legs():
+    out, n = [], 0
+    for w, sigma in zip(FOG_WEIGHTS, ("2.6", "8", "22", "79")):  # every strength with both grids, from both poses
+        n += 1
+        out.append(_fog_leg("strength", f"sigma{sigma}", "hot", "persistent", "near", w, n,
+                            frames=((None, 0), (None, 1), ("random", 0), ("random", 1))))
+    for i, (iname, (kw, own, stage, env)) in enumerate(INSTANCES.items()):
+        quad = iname in QUAD_INSTANCES
+        forms = ("none", "near", "far") if iname == "hot" else ((("none", "near") if own == WIDE else ("none", "near", "far"))[i % (2 if own == WIDE else 3)],) if quad else ("-",)
+        n += 1  # (both schedulers and every gather form of an instance render the same models: one restatement serves them)
+        for sched in ("persistent", "strip"):
+            for form in forms:
+                out.append(_fog_leg("instance", f"{iname}-{sched}" + (f"-{form}" if form != "-" else ""), iname, sched, form,
+                                    W3 if iname == "hot" else FOG_WEIGHTS[i % 4], n))
+    for j, (oname, (opts_kw, w)) in enumerate(FOG_OPTIONS.items()):
+        n += 1
+        out.append(_fog_leg("option", oname, "hot", ("persistent", "strip")[j % 2], "near", w, n, opts_kw=opts_kw))
+    for j, gname in enumerate(("bound4_cascade3", "ngp_aabb32")):
+        n += 1
+        out.append(_fog_leg("option", f"geometry-{gname}", "hot", ("persistent", "strip")[j % 2], "near", W3, n, geometry=gname))
+    hot_n = 5  # the route set of the hot instance legs: the legs below must equal their frames bit for bit
+    assert out[4]["instance"] == "hot" and out[4]["routes"] == _fog_leg("x", "x", "hot", "strip", "near", W3, hot_n)["routes"]
+    for sched in ("persistent", "strip"):
+        for sname, env in FOG_SWITCHES.items():
+            if sched == "strip" and sname == "tailsplit0":
+                continue  # (tail splitting is the persistent kernel's)
+            out.append(_fog_leg("switch", f"{sname}-{sched}", "hot", sched, "near", W3, hot_n, env=env, same_as_plain=True))
+        out.append(_fog_leg("output", f"rays-{sched}", "hot", sched, "near", W3, hot_n, option="rays", same_as_plain=True))
+    for opt in ("views3", "shard1of3", "u8"):
+        out.append(_fog_leg("output", opt, "hot", "persistent", "near", W3, hot_n, option=opt, same_as_plain=True))
+    for sched in ("persistent", "strip"):
+        out.append(_fog_leg("large", sched, "hot", sched, "near", W3, hot_n, size=FOG_LARGE))
+    return out
+
+
+FOG_LEGS = _fog_legs()
+
+
+def fog_options(leg):
+    o = nh.default_options()
+    for k, v in leg["opts_kw"].items():
+        setattr(o, k, v)
+    return o
+
+
+def fog_key(leg):
+    """What a leg's restatement depends on: legs that differ in scheduler, gather form, switches or output path share it."""
+    return (tuple(sorted(leg["build_kw"].items())), repr(leg["routes"]), leg["weight"], leg["frames"], tuple(sorted(leg["opts_kw"].items())),
+            leg["size"])
+
+
+def fog_models(leg):
+    """(desc, keep, info, pose) of every frame of a leg."""
+    all_poses = poses(2)
+    for grid, p in leg["frames"]:
+        desc, keep, info = probe_desc(leg["build_kw"], leg["routes"], grid, seed=3000, sigma_weight=leg["weight"])
+        yield desc, keep, info, all_poses[p]
