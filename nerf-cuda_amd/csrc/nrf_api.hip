@@ -286,12 +286,30 @@ struct ModelPlan {
   int own;                   // NET_*: the instance that renders the frames when its march tables fit (set_density_grid)
   int stage;                 // NET_HOT, NET_WIDE or NET_GENERIC: the stage entry points, the per-strip kernel, the fallback
   uint32_t quad_mask, quad_far;  // DevModel::quad_mask / quad_far
+  uint32_t uni_modes;        // DevModel::uni_modes
+  uint32_t gather_plan;      // DevModel::gather_plan: the static gather plan of the hot instance the steps' forms match, or GATHER_RUNTIME
   uint64_t table_ref_bytes;  // device bytes of the reference-order table
   uint64_t table_bytes;      // ... and of the quad copies behind it
 };
 
-// budget_mb: bytes of quad copies allowed (MiB); max_quad_steps: unrolled steps (four levels each) that may have them
-ModelPlan plan_model(const nrf_model_desc& d, bool allow_own, uint64_t budget_mb, int max_quad_steps) {
+// 2 bits per unrolled step jl of the fused kernel (DevModel::uni_modes): its existing levels are all dense (1) / all power-of-two hashed (2)
+uint32_t uni_modes_of(const LevelParams* lp, uint32_t L) {
+  uint32_t uni = 0;
+  for (int jl = 0; jl < 4; ++jl) {
+    bool all_dense = true, all_hash = true;
+    for (int g = 0; g < 4; ++g) {
+      if ((uint32_t)(4 * jl + g) >= L) continue;  // (a level the grid does not have: its lanes are masked, grid_features)
+      all_dense = all_dense && lp[4 * jl + g].mode == LV_DENSE;
+      all_hash = all_hash && lp[4 * jl + g].mode == LV_HASH_POW2;
+    }
+    uni |= (all_dense ? 1u : (all_hash ? 2u : 0u)) << (2 * jl);
+  }
+  return uni;
+}
+
+// budget_mb: bytes of quad copies allowed (MiB); max_quad_steps: unrolled steps (four levels each) that may have them;
+// static_gather: the hot instance may run under a static gather plan (NRF_GATHER_PLAN=0: never)
+ModelPlan plan_model(const nrf_model_desc& d, bool allow_own, uint64_t budget_mb, int max_quad_steps, bool static_gather = true) {
   ModelPlan p;
   std::memset(&p, 0, sizeof(p));
   p.rc = validate_model(d, p.lv);
@@ -435,6 +453,8 @@ ModelPlan plan_model(const nrf_model_desc& d, bool allow_own, uint64_t budget_mb
     }
     Lv.mask_b = (hashed_pow2 || Lv.mode == LV_ADD_POW2) ? ((Lv.size - 1) << sh_b) : 0xffffffffu;
   }
+  p.uni_modes = uni_modes_of(p.lp, L);
+  p.gather_plan = static_gather ? gather_plan_of(own, L, p.uni_modes, p.quad_mask, p.quad_far) : GATHER_RUNTIME;
   return p;
 }
 
@@ -475,6 +495,7 @@ struct nrf_context {
   std::vector<float> host_grid;  // the float density grid the march tables were built from
   bool grid_missing = false;     // loaded without a density grid and none generated yet
   bool allow_persistent = true;  // NRF_PERSISTENT=0 keeps the one-workgroup-per-strip render_kernel (A/B runs)
+  bool allow_gather_plan = true; // NRF_GATHER_PLAN=0: the hot instance selects every gather step's form at run time (GATHER_RUNTIME; A/B runs)
   bool centre_out = true;        // NRF_CENTRE_OUT=0: the persistent kernel's queue in row order
   bool allow_gen_wlds = true;    // NRF_GEN_WLDS=0: the generic instance's weight fragments are never staged in LDS
   bool allow_width_instances = true;  // NRF_WIDTH_INSTANCES=0: 16 / 32 / 128-neuron models render in the generic instance (A/B runs)
@@ -992,6 +1013,7 @@ int nrf_create(int device, nrf_context** out) {
   }
   if (const char* e = std::getenv("NRF_SAMPLE_CAP")) { c->sample_cap = std::atoi(e); c->sample_cap_forced = true; }
   if (const char* e = std::getenv("NRF_PERSISTENT")) c->allow_persistent = std::atoi(e) != 0;
+  if (const char* e = std::getenv("NRF_GATHER_PLAN")) c->allow_gather_plan = std::atoi(e) != 0;
   if (const char* e = std::getenv("NRF_CENTRE_OUT")) c->centre_out = std::atoi(e) != 0;
   if (const char* e = std::getenv("NRF_GEN_WLDS")) c->allow_gen_wlds = std::atoi(e) != 0;
   if (const char* e = std::getenv("NRF_WIDTH_INSTANCES")) c->allow_width_instances = std::atoi(e) != 0;
@@ -1080,7 +1102,8 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   }
   if (d->gather_copy_budget_mb) budget_mb = d->gather_copy_budget_mb;
   if (c->quad_budget_mb >= 0) budget_mb = (uint64_t)c->quad_budget_mb;
-  const ModelPlan p = plan_model(*d, c->allow_width_instances, budget_mb, c->quad_levels < 0 ? 4 : std::min(c->quad_levels, 16) / 4);
+  const ModelPlan p = plan_model(*d, c->allow_width_instances, budget_mb, c->quad_levels < 0 ? 4 : std::min(c->quad_levels, 16) / 4,
+                                     c->allow_gather_plan);
   if (p.rc) return p.rc;
   const nrf_level_table& lv = p.lv;
   // fp32 -> fp16 cast of every parameter (nerf_network.h:434-436), order: density MLP | rgb MLP | grid;
@@ -1203,18 +1226,11 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   M.sigma_activation = d->sigma_activation;
   M.rgb_activation = d->rgb_activation;
   M.rgb_output_activation = d->rgb_output_activation;
-  M.uni_modes = 0;
-  for (int jl = 0; jl < 4; ++jl) {
-    bool all_dense = true, all_hash = true;
-    for (int g = 0; g < 4; ++g) {
-      if ((uint32_t)(4 * jl + g) >= L) continue;  // (a level the grid does not have: its lanes are masked, grid_features)
-      all_dense = all_dense && lp[4 * jl + g].mode == LV_DENSE;
-      all_hash = all_hash && lp[4 * jl + g].mode == LV_HASH_POW2;
-    }
-    M.uni_modes |= (all_dense ? 1u : (all_hash ? 2u : 0u)) << (2 * jl);
-  }
+  M.uni_modes = p.uni_modes;
   M.quad_mask = quad_mask;
   M.quad_far = quad_far;
+  // (decided again from the copies the device had room for: without them the plan's instance would read quads that do not exist)
+  M.gather_plan = c->allow_gather_plan ? gather_plan_of(p.own, L, p.uni_modes, quad_mask, quad_far) : GATHER_RUNTIME;
   c->table_bytes = table_bytes;
   c->table_ref_bytes = p.table_ref_bytes;
   c->gather_addresses = 0;
@@ -1938,6 +1954,22 @@ extern "C" int nrf_debug_plan(const nrf_model_desc* d, int allow_own, uint64_t b
   const uint32_t v[6] = {(uint32_t)p.own, (uint32_t)p.stage, p.quad_mask, p.quad_far, (uint32_t)waves,
                          (uint32_t)render_persistent_lds_bytes(p.own, waves, p.gen_wave_bytes)};
   std::memcpy(out, v, sizeof(v));
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the gather plan plan_model chooses for a descriptor at that budget -- out = {plan
+// (0 = GATHER_RUNTIME), the four steps' forms (0 mixed, 1 dense, 2 hashed, 3 near quad, 4 far quad; of the static plan or, under
+// GATHER_RUNTIME, what the kernel selects at run time)}.  budget_mb = 0 is the default budget, as in nrf_model_desc.gather_copy_budget_mb
+// (QUAD_BUDGET_MB_DEFAULT: no device to ask).  NRF_GATHER_PLAN=0 in the environment forces GATHER_RUNTIME as it does for a context
+// (tests/test_gather_plan_cpu.py)
+extern "C" int nrf_debug_gather_plan(const nrf_model_desc* d, int allow_own, uint64_t budget_mb, uint32_t out[5]) {
+  if (!d || !d->params || !out) return fail(NRF_E_INVALID, "null argument");
+  const char* e = std::getenv("NRF_GATHER_PLAN");
+  const ModelPlan p = plan_model(*d, allow_own != 0, budget_mb ? budget_mb : (uint64_t)QUAD_BUDGET_MB_DEFAULT, 4, !(e && std::atoi(e) == 0));
+  if (p.rc) return p.rc;
+  out[0] = p.gather_plan;
+  for (int jl = 0; jl < 4; ++jl)
+    out[1 + jl] = ((p.quad_mask >> (4 * jl)) & 1u) ? (((p.quad_far >> jl) & 1u) ? GFORM_QUAD_FAR : GFORM_QUAD) : ((p.uni_modes >> (2 * jl)) & 3u);
   return NRF_OK;
 }
 

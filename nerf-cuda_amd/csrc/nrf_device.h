@@ -152,6 +152,8 @@ struct DevModel {
   uint32_t quad_far;        // bit jl: step jl's four levels have FAR quad copies (beyond a buffer resource's 4 GiB: level_gather_quad_far)
   uint32_t quad_mask;       // bit l: level l is gathered from its cell-major quad copy (level_gather_quad); granted four levels -- one unrolled
                             // step jl of the fused kernel, all of its lane groups -- at a time (nrf_load_model)
+  uint32_t gather_plan;     // host side only (launch_persistent_hot): GATHER_RUNTIME, or the static gather plan (nrf_launch.h) whose
+                            // instances render this model -- the kernels read quad_mask / quad_far / uni_modes or their own template argument
 };
 
 // One camera of a batched launch (nrf_render_views): what differs between the views of a batch.

@@ -17,6 +17,13 @@ namespace nrf {
   } while (0)
 
 hipError_t launch_persistent_hot(const PersistLaunch& L) {
+  // a model whose four gather steps have the forms of a static plan (plan_model) runs that plan's instances: same tile program,
+  // the steps' forms fixed at compile time (fast_interp has run-time instances only)
+  if (!L.P->fast_interp) {
+    if (L.M->gather_plan == GATHER_QQFH) return launch_persistent_hot_qqfh(L);
+    if (L.M->gather_plan == GATHER_QQHH) return launch_persistent_hot_qqhh(L);
+    if (L.M->gather_plan == GATHER_DMHH) return launch_persistent_hot_dmhh(L);
+  }
   if (L.unit) NRF_LAUNCH_HOT(MARCH_UNIT);
   else if (L.pow2) NRF_LAUNCH_HOT(MARCH_POW2);
   else NRF_LAUNCH_HOT(MARCH_GENERIC);
@@ -28,6 +35,9 @@ hipError_t launch_persistent_hot(const PersistLaunch& L) {
 void preload_hot() {
   hipFuncAttributes a;
   (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_persistent_kernel<NET_HOT, MARCH_UNIT, persist_waves(NET_HOT), false, false, false>));
+  preload_hot_qqfh();
+  preload_hot_qqhh();
+  preload_hot_dmhh();
 }
 
 }  // namespace nrf

@@ -11,9 +11,9 @@ namespace nrf {
   do {                                                                                                                   \
     constexpr int WV = persist_waves(NET_HOT);                                                                           \
     if (L.waves != WV) return hipErrorInvalidConfiguration; /* the host sized the workgroup's LDS for another instance */ \
-    hipError_t e_ = allow_lds(render_persistent_kernel<NET_HOT, U, WV, false, O8, true, false>, L.lds);                  \
+    hipError_t e_ = allow_lds(render_persistent_kernel<NET_HOT, U, WV, false, O8, true, GATHER_RUNTIME, false>, L.lds);                  \
     if (e_ != hipSuccess) return e_;                                                                                     \
-    hipLaunchKernelGGL((render_persistent_kernel<NET_HOT, U, WV, false, O8, true, false>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, \
+    hipLaunchKernelGGL((render_persistent_kernel<NET_HOT, U, WV, false, O8, true, GATHER_RUNTIME, false>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, \
                        *L.M, *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue);   \
   } while (0)
 #define NRF_LAUNCH_HOT_RAYS(U)                                                                                           \
@@ -60,7 +60,7 @@ hipError_t launch_strip_rays(const StripLaunch& L) {
 // nrf_load_model pays for it (once per process and device) and not the first frame (preload_kernels, nrf_kernels.hip)
 void preload_rays() {
   hipFuncAttributes a;
-  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_persistent_kernel<NET_HOT, MARCH_UNIT, persist_waves(NET_HOT), false, false, true, false>));
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&render_persistent_kernel<NET_HOT, MARCH_UNIT, persist_waves(NET_HOT), false, false, true, GATHER_RUNTIME, false>));
 }
 
 }  // namespace nrf

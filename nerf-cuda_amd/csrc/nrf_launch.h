@@ -23,6 +23,31 @@ __host__ __device__ constexpr int net_grid_f(int net) {
 }
 __host__ __device__ constexpr int net_width(int net) { return net == NET_W16 ? 16 : (net == NET_W32 ? 32 : (net == NET_W128 ? 128 : 64)); }
 
+// Gather plan: the form of each of a sample's four gather steps (levels 4 jl .. 4 jl + 3) as a COMPILE-TIME parameter of the hot
+// path.  GATHER_RUNTIME (the default of every template) selects each step's form at run time from DevModel::quad_mask / quad_far /
+// uni_modes (gather_step); a static plan names the four forms, so that the tile program has no control flow between a sample's
+// loads -- behind the run-time diamonds the compiler drains the memory counter in front of every step but the first
+// (profiles/r07/gather_plan_listing.txt).  Static plans exist for the NET_HOT persistent kernel only (nrf_kernels_hot_*.hip);
+// plan_model (nrf_api.hip: gather_plan_of) picks one when the model's steps have exactly its forms.
+enum : uint32_t { GFORM_MIXED = 0, GFORM_DENSE = 1, GFORM_HASHED = 2, GFORM_QUAD = 3, GFORM_QUAD_FAR = 4 };  // (0..2: uni_modes' values)
+__host__ __device__ constexpr uint32_t gather_plan(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t f3) {
+  return 0x10000u | f0 | (f1 << 4) | (f2 << 8) | (f3 << 12);
+}
+__host__ __device__ constexpr uint32_t gather_form(uint32_t plan, int jl) { return (plan >> (4 * jl)) & 15u; }
+constexpr uint32_t GATHER_RUNTIME = 0;
+constexpr uint32_t GATHER_QQFH = gather_plan(GFORM_QUAD, GFORM_QUAD, GFORM_QUAD_FAR, GFORM_HASHED);  // base.json's grid, default copy budget
+constexpr uint32_t GATHER_QQHH = gather_plan(GFORM_QUAD, GFORM_QUAD, GFORM_HASHED, GFORM_HASHED);    // near copies only (about 100 .. 256 MB)
+constexpr uint32_t GATHER_DMHH = gather_plan(GFORM_DENSE, GFORM_MIXED, GFORM_HASHED, GFORM_HASHED);  // no copies
+// the plan of a model's steps: one of the three static plans when `own` is NET_HOT and the forms match, else GATHER_RUNTIME
+inline uint32_t gather_plan_of(int own, uint32_t n_levels, uint32_t uni_modes, uint32_t quad_mask, uint32_t quad_far) {
+  if (own != NET_HOT || n_levels != 16) return GATHER_RUNTIME;
+  uint32_t f[4];
+  for (int jl = 0; jl < 4; ++jl)
+    f[jl] = ((quad_mask >> (4 * jl)) & 1u) ? (((quad_far >> jl) & 1u) ? GFORM_QUAD_FAR : GFORM_QUAD) : ((uni_modes >> (2 * jl)) & 3u);
+  const uint32_t plan = gather_plan(f[0], f[1], f[2], f[3]);
+  return plan == GATHER_QQFH || plan == GATHER_QQHH || plan == GATHER_DMHH ? plan : GATHER_RUNTIME;
+}
+
 struct DevModel;
 struct FrameParams;
 struct ViewBatch;

@@ -227,6 +227,21 @@ __device__ __forceinline__ void gather_step(const DevModel& M, const LevelParams
   else if (uni == 1u) level_gather<1>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
   else level_gather<0>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
 }
+// The same step in the form a static gather plan names for it (nrf_launch.h): no branch, so the loads of a sample's four steps
+// are one straight-line sequence and the compiler's wait insertion sees every one of them (a merge of run-time forms makes it
+// drain the memory counter in front of the next step's loads: profiles/r07/gather_plan_listing.txt)
+template <uint32_t GP, int JL>
+__device__ __forceinline__ void gather_step_static(const DevModel& M, const LevelParams* lvs, int g, float px, float py, float pz,
+                                                   uint32_t (&v)[8], float (&fr)[3]) {
+  constexpr uint32_t form = gather_form(GP, JL);
+  static_assert(form <= GFORM_QUAD_FAR, "a static gather plan names one of the five step forms");
+  const LevelParams L = lvs[4 * JL + g];
+  if constexpr (form == GFORM_QUAD_FAR) level_gather_quad_far(M.grid, L, px, py, pz, v, fr);
+  else if constexpr (form == GFORM_QUAD) level_gather_quad(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+  else if constexpr (form == GFORM_HASHED) level_gather<2>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+  else if constexpr (form == GFORM_DENSE) level_gather<1>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+  else level_gather<0>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+}
 __device__ __forceinline__ void sample_pos01(const DevModel& M, const float4 p, float& px, float& py, float& pz) {
   // xyz -> [0,1]: linear_transformer(1/(2 bound), 0.5), R/src/nerf_render.cu:311-312
   if (M.pos_w_pow2) {  // wave-uniform: the product cannot round, so the fma equals multiply-then-add
@@ -240,7 +255,7 @@ __device__ __forceinline__ void sample_pos01(const DevModel& M, const float4 p, 
   }
 }
 
-template <int NT, int RK = 1, bool FAST = false, int WD = 64, bool SHROWS = false, int DEPTH = 0, int GF = 0>
+template <int NT, int RK = 1, bool FAST = false, int WD = 64, bool SHROWS = false, int DEPTH = 0, int GF = 0, uint32_t GP = GATHER_RUNTIME>
 __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const float* rayd, int S, int base, int lane, float density_scale,
                                                  const half_t* rows = nullptr) {
@@ -260,14 +275,23 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
       // lane group g encodes levels {g, 4+g, 8+g, 12+g}: for each unrolled step jl the four groups work
       // on four ADJACENT levels, which for the usual tables are all dense (jl = 0) or all hashed
       // (jl >= 2), so the index arithmetic is specialised per step by a wave-uniform branch.
-      // all 32 gathers of the sample go out before the first one is consumed
+      // all gathers of the sample are meant to go out before the first one is consumed: with a static gather plan (GP) they
+      // do; with the run-time selection every step after the first waits for the loads before it (gather_step_static)
       if constexpr (GF != 0) {
         grid_features<GF>(M, lvs, px, py, pz, g, fb);
       } else {
       uint32_t gv[4][8];
       float gf[4][3];
+      if constexpr (GP != GATHER_RUNTIME) {
+        static_assert(RK == 1, "static gather plans exist for the hot instance only");
+        gather_step_static<GP, 0>(M, lvs, g, px, py, pz, gv[0], gf[0]);
+        gather_step_static<GP, 1>(M, lvs, g, px, py, pz, gv[1], gf[1]);
+        gather_step_static<GP, 2>(M, lvs, g, px, py, pz, gv[2], gf[2]);
+        gather_step_static<GP, 3>(M, lvs, g, px, py, pz, gv[3], gf[3]);
+      } else {
 #pragma unroll
       for (int jl = 0; jl < 4; ++jl) gather_step<RK, SHROWS>(M, lvs, jl, g, px, py, pz, gv[jl], gf[jl]);
+      }
 #pragma unroll
       for (int jl = 0; jl < 4; ++jl) fb[jl] = level_interp<FAST>(gv[jl], gf[jl]);
       }
@@ -369,7 +393,7 @@ __device__ __forceinline__ void gen_network_from_lds(const DevModel& M, const Ge
   gen_wave_sync();  // the next pass overwrites the rows
 }
 
-template <int NET, bool FAST = false>
+template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME>
 __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const GenLds& Lw, int S, int lane, float density_scale) {
   constexpr int RK = (NET == NET_WIDE || NET == NET_WIDE_SH) ? RK_WIDE : 1;
@@ -385,8 +409,8 @@ __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4*
       const int ntile = (S - base + 15) >> 4;
       constexpr int DP = NET == NET_DEPTH ? 1 : (NET == NET_ACT ? 2 : 0);  // (2: runtime hidden activations)
       constexpr int GF = net_grid_f(NET);
-      if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
-      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF, GP>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
     }
   }
 }
@@ -678,7 +702,8 @@ __device__ __forceinline__ uint32_t ray_number(const FrameParams& P, uint32_t pi
 // the hot persistent instance (128 VGPR + AGPR at 16 waves), so a live lane re-reads its origin at the top of every round's march --
 // the only phase that uses it -- from the origins of view rays_view (FrameParams::rays_o; 12 bytes per ray and round against ~512 per sample, L2-resident)
 // by the ray number its pix_idx stands for: o_in is ignored, and a ray handed to a helper wave needs no origin in its mail.
-template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false, bool RAYS = false>
+template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false, bool RAYS = false,
+          uint32_t GP = GATHER_RUNTIME>
 __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams& P, const MarchConst& mc, const LdsMap& lm,
                                             const uint32_t* coarse_lds, const float* ctab_lds, int lane, const float (&o_in)[3],
                                             const float (&d)[3], float rdx, float rdy, float rdz, int sx, int sy, int sz,
@@ -821,7 +846,7 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
 
     if (S > 0) {
       // ---- network on the S queued samples (sample-major MFMA tiles)
-      network_dispatch<NET, FAST>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
+      network_dispatch<NET, FAST, GP>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
       wave_sync();
     }
     NRF_STAMP(t2);
@@ -1242,7 +1267,9 @@ static_assert(offsetof(PersistArgs, P) == (sizeof(DevModel) + alignof(FrameParam
 // their own, so that the shipped default symbols keep the bit-exact arithmetic (tests/test_abi_cpu.py checks their ISA)
 // RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray; every view's region of interest is its whole frame) --
 // instances of their own, nrf_kernels_rays.hip.  (FAST stays the last argument: tests/test_abi_cpu.py reads it off the symbol names)
-template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, bool RAYS = false, bool FAST = false>
+// GP: the gather plan (nrf_launch.h) -- GATHER_RUNTIME, or one of the static plans of the hot instance (nrf_kernels_hot_*.hip)
+template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, bool RAYS = false,
+          uint32_t GP = GATHER_RUNTIME, bool FAST = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const DevModel M0, const FrameParams P0, const ViewBatch VB0,
                                                                               float4* __restrict__ rgba0, float* __restrict__ depth0,
                                                                               unsigned long long* __restrict__ counters,
@@ -1481,7 +1508,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
       wave_sync();
       NRF_STAMP(t_setup_done);
       const HelpArgs ha = {hl, lm.W - wave, view};
-      tile_rounds<NET, true, MARCH, true, FAST, false, RAYS>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m, t_skip,
+      tile_rounds<NET, true, MARCH, true, FAST, false, RAYS, GP>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m, t_skip,
                                                              t, tc, alive, acc, ts, 0, &ha, pix_idx, near, far, &given,
                                                              view);
 #ifdef NRF_PHASE_TIMING
@@ -1603,7 +1630,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const HelpArgs ha = {hl, lm.W - wave, view};
     // (t_skip: the occupancy lookups it would skip are of cells known to be empty -- looking them up changes nothing)
     // (RAYS: a helped ray's origin is re-read by its number -- pix_idx -- like every other ray's, tile_rounds)
-    tile_rounds<NET, true, MARCH, true, FAST, false, RAYS>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m,
+    tile_rounds<NET, true, MARCH, true, FAST, false, RAYS, GP>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz, far_m,
                                                            -3.402823466e+38f, t, tc, mine, acc, ts, n_ray_samples, &ha, pix_idx, near, far, &given,
                                                            view);
     const OutPlanes op = view_planes<OUT8>(P, rgba0, depth0, view, VB.view_stride_px);
@@ -1686,6 +1713,10 @@ struct PersistLaunch {
   bool unit, pow2;  // march form: one cascade with mip_bound 1 / several cascades with a power-of-two bound (else generic)
 };
 hipError_t launch_persistent_hot(const PersistLaunch& L);
+// the hot instance under a static gather plan (DevModel::gather_plan), a translation unit each: nrf_kernels_hot_qqfh.hip, ..qqhh, ..dmhh
+hipError_t launch_persistent_hot_qqfh(const PersistLaunch& L);
+hipError_t launch_persistent_hot_qqhh(const PersistLaunch& L);
+hipError_t launch_persistent_hot_dmhh(const PersistLaunch& L);
 hipError_t launch_persistent_width(const PersistLaunch& L);
 hipError_t launch_persistent_wide(const PersistLaunch& L);
 hipError_t launch_persistent_generic(const PersistLaunch& L);
@@ -1704,6 +1735,9 @@ struct StripLaunch {
 hipError_t launch_strip(const StripLaunch& L);
 hipError_t launch_strip_rays(const StripLaunch& L);  // FrameParams::rays_o != nullptr (nrf_kernels_rays.hip)
 void preload_hot();
+void preload_hot_qqfh();
+void preload_hot_qqhh();
+void preload_hot_dmhh();
 void preload_width();
 void preload_wide();
 void preload_generic();
@@ -1712,14 +1746,35 @@ void preload_grid();
 void preload_rays();
 
 // one instance of the persistent form: WV waves per workgroup, WL = generic weights in LDS, 8-bit output / fast_interp chosen at run time
-#define NRF_LAUNCH_PERSISTENT_F(G, U, WV, WL, O8, FI)                                                                    \
+// (GP: the gather plan, nrf_launch.h)
+#define NRF_LAUNCH_PERSISTENT_G(G, U, WV, WL, O8, GP, FI)                                                                \
   do {                                                                                                                   \
     if (L.waves != (WV)) return hipErrorInvalidConfiguration; /* the host sized the workgroup's LDS for another instance */ \
-    hipError_t e_ = allow_lds(render_persistent_kernel<G, U, WV, WL, O8, false, FI>, L.lds);                                    \
+    hipError_t e_ = allow_lds(render_persistent_kernel<G, U, WV, WL, O8, false, GP, FI>, L.lds);                         \
     if (e_ != hipSuccess) return e_;                                                                                     \
-    hipLaunchKernelGGL((render_persistent_kernel<G, U, WV, WL, O8, false, FI>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, *L.M,  \
+    hipLaunchKernelGGL((render_persistent_kernel<G, U, WV, WL, O8, false, GP, FI>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, *L.M, \
                        *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue);         \
   } while (0)
+#define NRF_LAUNCH_PERSISTENT_F(G, U, WV, WL, O8, FI) NRF_LAUNCH_PERSISTENT_G(G, U, WV, WL, O8, GATHER_RUNTIME, FI)
+// The hot instance under the static gather plan GP: its launcher and its code object's preload, one translation unit per plan
+// (FAST = false only: fast_interp keeps the run-time selection, nrf_kernels_hot.hip)
+#define NRF_LAUNCH_HOT_PLAN(U, GP)                                                                                       \
+  do {                                                                                                                   \
+    if (L.P->out_mode == OUT_U8) NRF_LAUNCH_PERSISTENT_G(NET_HOT, U, persist_waves(NET_HOT), false, true, GP, false);    \
+    else NRF_LAUNCH_PERSISTENT_G(NET_HOT, U, persist_waves(NET_HOT), false, false, GP, false);                           \
+  } while (0)
+#define NRF_DEFINE_HOT_PLAN(NAME, GP)                                                                                    \
+  hipError_t launch_persistent_hot_##NAME(const PersistLaunch& L) {                                                      \
+    if (L.unit) NRF_LAUNCH_HOT_PLAN(MARCH_UNIT, GP);                                                                     \
+    else if (L.pow2) NRF_LAUNCH_HOT_PLAN(MARCH_POW2, GP);                                                                \
+    else NRF_LAUNCH_HOT_PLAN(MARCH_GENERIC, GP);                                                                         \
+    return hipGetLastError();                                                                                            \
+  }                                                                                                                      \
+  void preload_hot_##NAME() {                                                                                            \
+    hipFuncAttributes a;                                                                                                 \
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(                                                        \
+                                       &render_persistent_kernel<NET_HOT, MARCH_UNIT, persist_waves(NET_HOT), false, false, false, GP, false>)); \
+  }
 #define NRF_LAUNCH_PERSISTENT_W(G, U, WV, WL)                                                                            \
   do {                                                                                                                   \
     if (L.P->out_mode == OUT_U8) NRF_LAUNCH_PERSISTENT_F(G, U, WV, WL, true, false);                                     \

@@ -1,12 +1,14 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): kernel-trace stats and PMC passes of bench.py.
 # Usage: scripts/profile_gpu.sh <tag>   -> writes gpurun_out/prof_<tag>/*
+# Environment: LIB=<another libnerfhip.so> profiles that build on the same box (the "before" of an A/B);
+# RENDER_ONLY=1 skips the fused-MLP stage kernel's passes
 set -eo pipefail
 TAG=${1:-r01}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 $PWD/bench.py --full --steps 8 --warmup 2 --no-extras"  # launch order trace_summary.py expects: timed, 8 single views, step replay
+BENCH="python3 $PWD/bench.py --full --steps 8 --warmup 2 --no-extras${LIB:+ --lib $LIB}"  # launch order trace_summary.py expects: timed, 8 single views, step replay
 OLDPWD=$PWD
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- $BENCH > "$OUT/stats.log" 2>&1
@@ -32,6 +34,7 @@ pass tcp2 TCP_TCP_TA_DATA_STALL_CYCLES_sum TCP_READ_TAGCONFLICT_STALL_CYCLES_sum
 pass tcp3 TCP_TA_TCP_STATE_READ_sum || true
 # counter-side MFMA utilisation: the render kernel (bench.py) and the fused-MLP stage kernel alone (scripts/mlp_steady.py)
 pass mfma SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE || true
+if [ -n "$RENDER_ONLY" ]; then echo profile done; exit 0; fi
 MLP="python3 $OLDPWD/scripts/mlp_steady.py"
 mlp_pass() { n=$1; shift; timeout -k 10 180 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/pmc_mlp_$n" -- $MLP > "$OUT/pmc_mlp_$n.log" 2>&1; }
 mlp_pass a SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY || true
