@@ -1973,6 +1973,18 @@ extern "C" int nrf_debug_gather_plan(const nrf_model_desc* d, int allow_own, uin
   return NRF_OK;
 }
 
+// Diagnostic (not part of include/nerfhip.h): the LDS schedule (nrf_launch.h) of the persistent hot instance compiled for gather
+// plan `plan` and march form `form` -- out = {1 if it reads its levels from the staged compact blocks, the depth of its weight
+// fragment prefetch}; {0, 0} for GATHER_RUNTIME, which every other instance is compiled with (tests/test_lds_schedule_cpu.py)
+extern "C" int nrf_debug_lds_schedule(uint32_t plan, int form, uint32_t out[2]) {
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (plan != GATHER_RUNTIME && plan != GATHER_QQFH && plan != GATHER_QQHH && plan != GATHER_DMHH) return fail(NRF_E_INVALID, "not a gather plan");
+  if (form != MARCH_FORM_GENERIC && form != MARCH_FORM_UNIT && form != MARCH_FORM_POW2) return fail(NRF_E_INVALID, "not a march form");
+  out[0] = plan_levels(plan) ? 1u : 0u;
+  out[1] = (uint32_t)plan_frag_depth(plan, form);
+  return NRF_OK;
+}
+
 // Diagnostic build: entry / exit stamps (s_memtime) of the persistent kernel's waves, 2 x n values.
 extern "C" int nrf_debug_wave_times(nrf_context* c, unsigned long long* out, int n_waves) {
   if (!c || !out || n_waves < 1 || n_waves > 4096) return fail(NRF_E_INVALID, "bad argument");

@@ -1235,12 +1235,36 @@ struct MlpOut {
 // (An explicit issue order for this body -- one MFMA, then k vector instructions, by __builtin_amdgcn_sched_group_barrier -- was
 //  measured in round 3 and removed: k = 2 equals the compiler's own schedule, k = 3 / 4 are 5-7 % slower,
 //  profiles/r03/mlp_interleave.txt.)
-template <int NT, int D0_BASE = FRAG_D0, typename Frags = LdsFrags, int RK = 1, int W = 64>
-__device__ __forceinline__ void mlp_tiles(const Frags frag, const half8_t (&feat)[NT], const half4_t (&dirf)[NT], MlpOut<NT>& out,
-                                          bool rgb_sigmoid = false, const half8_t (*dirx)[RK_WIDE - 1] = nullptr) {
+// PF > 0 (static-plan hot instances, round 8): a rolling prefetch of the weight fragments -- the layers read them in the order
+// D0_BASE .. D0_BASE + MT - 1, then S::D1 .. S::N - 1, and fragment f + PF is read from LDS before the MFMAs of fragment f issue,
+// across layer boundaries and repack(); `pre` = the first PF fragments, which the caller has read already.  The order is pinned
+// by scheduling barriers that LDS reads and MFMAs may not cross (everything else may); the waits stay the compiler's.
+template <int NT, int D0_BASE = FRAG_D0, typename Frags = LdsFrags, int RK = 1, int W = 64, int PF = 0>
+__device__ __forceinline__ void mlp_tiles(const Frags frag_lds, const half8_t (&feat)[NT], const half4_t (&dirf)[NT], MlpOut<NT>& out,
+                                          bool rgb_sigmoid = false, const half8_t (*dirx)[RK_WIDE - 1] = nullptr,
+                                          const half8_t* pre = nullptr) {
   static_assert(NT == 1 || NT == 2 || NT == 4, "tiles per pass");
+  static_assert(PF == 0 || RK == 1, "the fragment prefetch covers the fragments 0 .. S::N - 1");
   using S = MlpShape<W>;
   constexpr int MT = S::MT, KS = S::KS;
+  half8_t wq[PF > 0 ? PF : 1];
+  int wn = 0;  // fragments taken so far (a constant in the unrolled body)
+  if constexpr (PF > 0) {
+#pragma unroll
+    for (int i = 0; i < PF; ++i) wq[i] = pre[i];
+  }
+  auto frag = [&](int f) -> half8_t {
+    if constexpr (PF > 0) {
+      const half8_t a = wq[wn % PF];
+      const int ahead = wn + PF;  // position in the reading order: the first MT are the D0_BASE fragments
+      if (ahead < S::N) wq[wn % PF] = frag_lds(ahead < MT ? D0_BASE + ahead : ahead);
+      ++wn;
+      __builtin_amdgcn_sched_barrier(0x676);  // may cross: VALU, SALU, VMEM, DS writes, transcendentals
+      return a;
+    } else {
+      return frag_lds(f);
+    }
+  };
   const float4_t zero = {0.f, 0.f, 0.f, 0.f};
   float4_t acc[NT][MT];
   half8_t hb[NT][KS];

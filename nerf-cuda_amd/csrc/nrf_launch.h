@@ -96,6 +96,24 @@ inline int march_form(uint32_t H, uint32_t cascade, float bound) {
   if (pow2_h && cascade > 1 && bound >= 1.0f && frexpf(bound, &eb) == 0.5f) return MARCH_FORM_POW2;    // several, power-of-two bound
   return MARCH_FORM_GENERIC;
 }
+// LDS schedule of the static-plan instances (round 8; NRF_LDS_PARAMS / NRF_LDS_FRAG_DEPTH may be overridden for A/B builds):
+//   PLAN_LEVELS  the kernel stages, in the level table's region, a compact 32-byte block per level laid out for the form its
+//                plan names (nrf_render.h: stage_plan_level) instead of LevelParams: what a lane needs of a level is ONE aligned 16-byte LDS
+//                read (two for the mixed form), and a tile's four reads go out together ahead of its first gather load
+//   FRAG_DEPTH   mlp_tiles reads weight fragment f + FRAG_DEPTH before the MFMAs of fragment f issue (nrf_device.h)
+#ifndef NRF_LDS_PARAMS
+#define NRF_LDS_PARAMS 1
+#endif
+#ifndef NRF_LDS_FRAG_DEPTH
+#define NRF_LDS_FRAG_DEPTH 2
+#endif
+#ifndef NRF_LDS_FRAG_DEPTH_GENERIC
+#define NRF_LDS_FRAG_DEPTH_GENERIC (NRF_LDS_FRAG_DEPTH > 1 ? 1 : NRF_LDS_FRAG_DEPTH)  // MARCH_GENERIC has no registers for two
+#endif
+__host__ __device__ constexpr bool plan_levels(uint32_t gp) { return gp != GATHER_RUNTIME && NRF_LDS_PARAMS != 0; }
+__host__ __device__ constexpr int plan_frag_depth(uint32_t gp, int march) {
+  return gp == GATHER_RUNTIME ? 0 : (march == MARCH_FORM_GENERIC ? NRF_LDS_FRAG_DEPTH_GENERIC : NRF_LDS_FRAG_DEPTH);
+}
 // waves of the persistent workgroup of instance `net` with that march form (NET_GENERIC may also run with 8: set_density_grid
 // tries 12 first), and its LDS bytes without the march tables (gen_wave_bytes: the generic instance's per-wave rows)
 int render_persist_waves(int net, int form);

@@ -242,6 +242,54 @@ __device__ __forceinline__ void gather_step_static(const DevModel& M, const Leve
   else if constexpr (form == GFORM_DENSE) level_gather<1>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
   else level_gather<0>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
 }
+// words of level l's block: quad forms {scale, q_off_b, q_my_b, q_mz_b} (the far form's q_max is q_my_b - 1: both are functions
+// of res, nrf_api.hip), hashed {scale, off_b, mask_b, -}, dense and mixed {scale, off_b, my_b, mz_b}, mixed also {mask_b, mode, -, -}
+static_assert(MARCH_GENERIC == MARCH_FORM_GENERIC && MARCH_UNIT == MARCH_FORM_UNIT && MARCH_POW2 == MARCH_FORM_POW2, "plan_frag_depth's march form");
+static_assert(LDS_LEVEL_BYTES >= 16 * 32, "the staged plan levels live in the level table's region");
+template <uint32_t GP>
+__device__ __forceinline__ void stage_plan_level(LevelParams* lvs, uint32_t l, const LevelParams L) {
+  const uint32_t form = gather_form(GP, (int)(l >> 2));
+  const uint32_t sc = __builtin_bit_cast(uint32_t, L.scale);
+  uint4 a, b = make_uint4(L.mask_b, L.mode, 0u, 0u);
+  if (form == GFORM_QUAD || form == GFORM_QUAD_FAR) a = make_uint4(sc, L.q_off_b, L.q_my_b, L.q_mz_b);
+  else if (form == GFORM_HASHED) a = make_uint4(sc, L.off_b, L.mask_b, 0u);
+  else a = make_uint4(sc, L.off_b, L.my_b, L.mz_b);
+  uint4* blk = reinterpret_cast<uint4*>(lvs) + 2 * l;
+  blk[0] = a;
+  blk[1] = b;
+}
+// this lane's level of step JL, read back from the staged block: the fields the step's form uses (the others are never read)
+template <uint32_t GP, int JL>
+__device__ __forceinline__ LevelParams plan_level(const LevelParams* lvs, int g) {
+  constexpr uint32_t form = gather_form(GP, JL);
+  const uint4* blk = reinterpret_cast<const uint4*>(lvs) + 2 * (4 * JL + g);
+  const uint4 a = blk[0];
+  LevelParams L = {};
+  L.scale = __builtin_bit_cast(float, a.x);
+  if constexpr (form == GFORM_QUAD || form == GFORM_QUAD_FAR) {
+    L.q_off_b = a.y; L.q_my_b = a.z; L.q_mz_b = a.w;
+    if constexpr (form == GFORM_QUAD_FAR) L.q_max = a.z - 1u;
+  } else if constexpr (form == GFORM_HASHED) {
+    L.off_b = a.y; L.mask_b = a.z;
+  } else {
+    L.off_b = a.y; L.my_b = a.z; L.mz_b = a.w;
+    if constexpr (form == GFORM_MIXED) {
+      const uint4 b = blk[1];
+      L.mask_b = b.x; L.mode = b.y;
+    }
+  }
+  return L;
+}
+template <uint32_t GP, int JL>
+__device__ __forceinline__ void gather_step_level(const DevModel& M, const LevelParams& L, float px, float py, float pz,
+                                                  uint32_t (&v)[8], float (&fr)[3]) {
+  constexpr uint32_t form = gather_form(GP, JL);
+  if constexpr (form == GFORM_QUAD_FAR) level_gather_quad_far(M.grid, L, px, py, pz, v, fr);
+  else if constexpr (form == GFORM_QUAD) level_gather_quad(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+  else if constexpr (form == GFORM_HASHED) level_gather<2>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+  else if constexpr (form == GFORM_DENSE) level_gather<1>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+  else level_gather<0>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
+}
 __device__ __forceinline__ void sample_pos01(const DevModel& M, const float4 p, float& px, float& py, float& pz) {
   // xyz -> [0,1]: linear_transformer(1/(2 bound), 0.5), R/src/nerf_render.cu:311-312
   if (M.pos_w_pow2) {  // wave-uniform: the product cannot round, so the fma equals multiply-then-add
@@ -255,7 +303,8 @@ __device__ __forceinline__ void sample_pos01(const DevModel& M, const float4 p, 
   }
 }
 
-template <int NT, int RK = 1, bool FAST = false, int WD = 64, bool SHROWS = false, int DEPTH = 0, int GF = 0, uint32_t GP = GATHER_RUNTIME>
+template <int NT, int RK = 1, bool FAST = false, int WD = 64, bool SHROWS = false, int DEPTH = 0, int GF = 0, uint32_t GP = GATHER_RUNTIME,
+          int PF = 0>
 __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const float* rayd, int S, int base, int lane, float density_scale,
                                                  const half_t* rows = nullptr) {
@@ -263,13 +312,26 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
   half8_t feat[NT];
   half4_t dirf[NT];
   half8_t dirx[NT][RK_WIDE - 1];
+  half8_t wpre[PF > 0 ? PF : 1];  // PF > 0: the first PF weight fragments, read behind the last tile's gathers (mlp_tiles)
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
     const int slot = base + 16 * n + c;
     uint32_t fb[4] = {0u, 0u, 0u, 0u};
     uint2 db = make_uint2(0u, 0u);
+    uint32_t lastv[8];
+    float lastf[3];
     if (slot < S) {
       const float4 p = W->pos[slot];
+      // (static plans) the tile's four level reads in one go, right behind the position's and ahead of everything that waits
+      // for it: one LDS round trip in front of the tile's loads, and nothing but address arithmetic between them
+      LevelParams PL[4];
+      if constexpr (plan_levels(GP) && GF == 0) {
+        PL[0] = plan_level<GP, 0>(lvs, g);
+        PL[1] = plan_level<GP, 1>(lvs, g);
+        PL[2] = plan_level<GP, 2>(lvs, g);
+        PL[3] = plan_level<GP, 3>(lvs, g);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       float px, py, pz;
       sample_pos01(M, p, px, py, pz);
       // lane group g encodes levels {g, 4+g, 8+g, 12+g}: for each unrolled step jl the four groups work
@@ -282,7 +344,18 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
       } else {
       uint32_t gv[4][8];
       float gf[4][3];
-      if constexpr (GP != GATHER_RUNTIME) {
+      if constexpr (plan_levels(GP)) {
+        static_assert(RK == 1, "static gather plans exist for the hot instance only");
+        // (the steps' loads keep their order -- vector-memory instructions may not cross these barriers, all else may --: the
+        //  interpolation consumes them step by step, behind a counted wait each)
+        gather_step_level<GP, 0>(M, PL[0], px, py, pz, gv[0], gf[0]);
+        __builtin_amdgcn_sched_barrier(0x78f);
+        gather_step_level<GP, 1>(M, PL[1], px, py, pz, gv[1], gf[1]);
+        __builtin_amdgcn_sched_barrier(0x78f);
+        gather_step_level<GP, 2>(M, PL[2], px, py, pz, gv[2], gf[2]);
+        __builtin_amdgcn_sched_barrier(0x78f);
+        gather_step_level<GP, 3>(M, PL[3], px, py, pz, gv[3], gf[3]);
+      } else if constexpr (GP != GATHER_RUNTIME) {
         static_assert(RK == 1, "static gather plans exist for the hot instance only");
         gather_step_static<GP, 0>(M, lvs, g, px, py, pz, gv[0], gf[0]);
         gather_step_static<GP, 1>(M, lvs, g, px, py, pz, gv[1], gf[1]);
@@ -293,7 +366,15 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
       for (int jl = 0; jl < 4; ++jl) gather_step<RK, SHROWS>(M, lvs, jl, g, px, py, pz, gv[jl], gf[jl]);
       }
 #pragma unroll
-      for (int jl = 0; jl < 4; ++jl) fb[jl] = level_interp<FAST>(gv[jl], gf[jl]);
+      for (int jl = 0; jl < 4; ++jl) {
+        if (PF > 0 && n == NT - 1 && jl == 3) {  // interpolated below, behind the MLPs' first fragment reads
+#pragma unroll
+          for (int k = 0; k < 8; ++k) lastv[k] = gv[3][k];
+          lastf[0] = gf[3][0]; lastf[1] = gf[3][1]; lastf[2] = gf[3][2];
+        } else {
+          fb[jl] = level_interp<FAST>(gv[jl], gf[jl]);
+        }
+      }
       }
       const int ray = __builtin_bit_cast(int, p.w);
       db = *reinterpret_cast<const uint2*>(&W->dirf[ray][2 * g]);
@@ -314,6 +395,17 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
 #pragma unroll
       for (int s = 1; s < RK; ++s) dirx[n][s - 1] = z8;
     }
+    if constexpr (PF > 0) {
+      // every lane reads the MLPs' first fragments (an A operand spans the wave) while the last tile's last step is still to be
+      // interpolated: steps 0..2 have returned their registers by then
+      if (n == NT - 1) {
+        const LdsFrags frag{wl, lane};
+#pragma unroll
+        for (int f = 0; f < PF; ++f) wpre[f] = frag(FRAG_D0 + f);
+        __builtin_amdgcn_sched_barrier(0);
+        if (slot < S) fb[3] = level_interp<FAST>(lastv, lastf);
+      }
+    }
     const uint4 fv = make_uint4(fb[0], fb[1], fb[2], fb[3]);
     feat[n] = __builtin_bit_cast(half8_t, fv);
     dirf[n] = __builtin_bit_cast(half4_t, db);
@@ -322,6 +414,10 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
   if constexpr (DEPTH == 2) mlp_tiles_depth<NT, LdsFragsPlain, true>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, M.depth_xd,
                                                                      M.depth_xr, M.density_activation, M.rgb_activation);
   else if constexpr (DEPTH == 1) mlp_tiles_depth<NT>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, M.depth_xd, M.depth_xr);
+  else if constexpr (WD == 64 && PF > 0) {
+    static_assert(RK == 1, "the fragment prefetch exists for the hot instance only");
+    mlp_tiles<NT, FRAG_D0, LdsFrags, 1, 64, PF>(LdsFrags{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, nullptr, wpre);
+  }
   else if constexpr (WD == 64) mlp_tiles<NT, FRAG_D0, LdsFrags, RK>(LdsFrags{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, dirx);
   else mlp_tiles<NT, 0, LdsFragsPlain, 1, WD>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID);
   if (g == 0) {  // decompose_network_in_and_out (render_utils.h:308-334): fp16 rows 0..2 -> fp32 rgb
@@ -393,7 +489,7 @@ __device__ __forceinline__ void gen_network_from_lds(const DevModel& M, const Ge
   gen_wave_sync();  // the next pass overwrites the rows
 }
 
-template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME>
+template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME, int PF = 0>
 __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const GenLds& Lw, int S, int lane, float density_scale) {
   constexpr int RK = (NET == NET_WIDE || NET == NET_WIDE_SH) ? RK_WIDE : 1;
@@ -409,8 +505,8 @@ __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4*
       const int ntile = (S - base + 15) >> 4;
       constexpr int DP = NET == NET_DEPTH ? 1 : (NET == NET_ACT ? 2 : 0);  // (2: runtime hidden activations)
       constexpr int GF = net_grid_f(NET);
-      if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF, GP>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
-      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF, GP, PF>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP, PF>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
     }
   }
 }
@@ -846,7 +942,7 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
 
     if (S > 0) {
       // ---- network on the S queued samples (sample-major MFMA tiles)
-      network_dispatch<NET, FAST, GP>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
+      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH)>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
       wave_sync();
     }
     NRF_STAMP(t2);
@@ -1303,7 +1399,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
   for (uint32_t i = threadIdx.x; i < M.lds_coarse_words; i += blockDim.x) coarse_lds[i] = M.occ_coarse[i];
   for (uint32_t i = threadIdx.x; i < M.lds_ctab_floats; i += blockDim.x) ctab_lds[i] = M.cell_bound[i];
   for (uint32_t i = threadIdx.x; i < M.lds_dilated_words; i += blockDim.x) dil_lds[i] = M.occ_dilated[i];
-  if (threadIdx.x < 16) lm.lvs[threadIdx.x] = M.lv[threadIdx.x];
+  if constexpr (plan_levels(GP)) {  // the level table in the plan's compact form (network_from_lds is its only reader here)
+    if (threadIdx.x < 16) stage_plan_level<GP>(lm.lvs, threadIdx.x, M.lv[threadIdx.x]);
+  } else {
+    if (threadIdx.x < 16) lm.lvs[threadIdx.x] = M.lv[threadIdx.x];
+  }
   if (threadIdx.x <= MAX_VIEWS) {
     const int v = (int)threadIdx.x;
     q_lds[v] = v < VB.n_views ? VB.v[v].q_begin : VB.q_total;
