@@ -275,6 +275,11 @@ int validate_model(const nrf_model_desc& d, nrf_level_table& lv) {
   return NRF_OK;
 }
 
+// log2 of the side of the coarse occupancy blocks (4 x 4 x 4 cells per bit), 0 where the grid has none: a side that is no multiple
+// of 4.  Without the coarse level no march table is staged in LDS (set_density_grid) and the model renders in the per-strip
+// kernel, whatever its gather plan: the static-plan instances are the persistent kernel's (nrf_debug_march_form)
+inline uint32_t march_coarse_shift(uint32_t H) { return (H % 4 == 0 && H >= 8) ? 2u : 0u; }
+
 // What a model descriptor makes of the device side, decided without a device (nrf_debug_plan: tests/test_instance_plan_cpu.py).
 struct ModelPlan {
   int rc;                    // NRF_OK, or the refusal (fail() has set the message)
@@ -751,7 +756,7 @@ int set_density_grid(nrf_context* c, const float* density_grid, float mean_densi
   // march tables (nrf_device.h march_next): coarse occupancy = OR over 4x4x4 cell blocks, and the
   // cell-boundary table ((v/(H-1))*2-1)*mip_bound in the reference's fp32 operation order
   const uint32_t Hs = d->density_grid_size, Cs = d->cascade;
-  const uint32_t coarse_shift = (Hs % 4 == 0 && Hs >= 8) ? 2u : 0u;
+  const uint32_t coarse_shift = march_coarse_shift(Hs);
   std::vector<uint32_t> coarse;
   if (coarse_shift) {
     const uint32_t Hc = Hs >> 2;
@@ -1973,6 +1978,14 @@ extern "C" int nrf_debug_gather_plan(const nrf_model_desc* d, int allow_own, uin
   return NRF_OK;
 }
 
+// Diagnostic (not part of include/nerfhip.h): the gather plan the context's loaded model launches with (DevModel::gather_plan, made
+// from the copies the device really granted and the context's NRF_GATHER_PLAN) -- a static plan's id or 0 = GATHER_RUNTIME; -1
+// without a model.  The persistent hot kernel alone reads it: nrf_debug_instance tells whether that kernel runs
+extern "C" long long nrf_debug_context_gather_plan(nrf_context* c) {
+  if (!c || !c->model_loaded) return -1;
+  return (long long)c->dm.gather_plan;
+}
+
 // Diagnostic (not part of include/nerfhip.h): the LDS schedule (nrf_launch.h) of the persistent hot instance compiled for gather
 // plan `plan` and march form `form` -- out = {1 if it reads its levels from the staged compact blocks, the depth of its weight
 // fragment prefetch}; {0, 0} for GATHER_RUNTIME, which every other instance is compiled with (tests/test_lds_schedule_cpu.py)
@@ -1982,6 +1995,16 @@ extern "C" int nrf_debug_lds_schedule(uint32_t plan, int form, uint32_t out[2]) 
   if (form != MARCH_FORM_GENERIC && form != MARCH_FORM_UNIT && form != MARCH_FORM_POW2) return fail(NRF_E_INVALID, "not a march form");
   out[0] = plan_levels(plan) ? 1u : 0u;
   out[1] = (uint32_t)plan_frag_depth(plan, form);
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the march side of the instance choice for a grid of side H with `cascade` cascades and
+// that bound -- out = {march_form (nrf_launch.h: 0 generic, 1 unit, 2 power of two), 1 if the grid has the coarse occupancy
+// level the march tables in LDS -- and with them the persistent kernel -- need (march_coarse_shift)} (tests/test_plan_matrix_cpu.py)
+extern "C" int nrf_debug_march_form(uint32_t H, uint32_t cascade, float bound, uint32_t out[2]) {
+  if (!out || H == 0 || cascade == 0 || !(bound > 0.0f)) return fail(NRF_E_INVALID, "bad argument");
+  out[0] = (uint32_t)march_form(H, cascade, bound);
+  out[1] = march_coarse_shift(H) ? 1u : 0u;
   return NRF_OK;
 }
 

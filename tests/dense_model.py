@@ -160,7 +160,10 @@ CERTIFIED_SHARE = {
     "w16": 0.99, "w32": 0.99, "w128": 0.99, "depth_d2_2": 0.99, "depth_d3_4": 0.99, "depth_d1_1": 0.99, "act_none": 0.99,
     "grid1_g1_16": 0.99, "grid2_g2_11": 0.99, "grid4_g4_8": 0.99, "grid8_g8_4": 0.99, "grid4_g4_6s": 0.99, "grid2_g2_16n": 0.99,
     "generic_w32_width_instances_off": 0.99, "generic_w32_h2": 0.99,
+    # the plan matrix (base.json's 2^19 table, one model x two frames per march cell: test_plan_matrix_cpu.py)
+    "plan-unit": 0.99, "plan-pow2": 0.99, "plan-generic_h": 0.99, "plan-generic_b": 0.99,
 }
+PLAN_SEED = 4000  # (the plan-matrix legs: one model per cell, kept by the rule above)
 
 
 def _leg(name, sched, option=None, size=(pm.FRAME_W, pm.FRAME_H), n_seeds=2, frames=FRAMES):
@@ -174,12 +177,24 @@ def _leg(name, sched, option=None, size=(pm.FRAME_W, pm.FRAME_H), n_seeds=2, fra
                 seeds=tuple(seeds), frames=tuple(frames), s=S)
 
 
+def _plan_leg(plan, cell):
+    """The hot instance under static plan `plan` in march cell `cell` (pm.PLANS, pm.PLAN_CELLS): encodings read in the plan's
+    forms in front of both MLPs.  A cell's three plans render the same model."""
+    gather = pm.PLANS[plan][0]
+    genv, budget, addresses = pm.GATHER[gather]
+    return dict(id=f"dense-plan-{plan}-{cell}", instance="hot", share="plan-" + cell, sched=pm.plan_sched(cell),
+                build_kw=dict(pm.T19, **pm.PLAN_CELLS[cell][0]), own=pm.HOT, stage=pm.HOT, env=dict(pm.PERSISTENT, **genv),
+                budget_mb=budget, addresses=addresses, option=None, size=(pm.FRAME_W, pm.FRAME_H), seeds=(PLAN_SEED,), frames=tuple(FRAMES),
+                s=S, **pm.plan_fields(plan, cell))
+
+
 def _legs():
     out = [_leg(name, sched) for name in pm.INSTANCES for sched in ("persistent", "strip")]
     out.append(_leg("w128", "persistent", option="views3"))
     out.append(_leg("depth_d3_4", "persistent", option="shard1of3"))
     for name in ("hot", "w32"):  # several strips per queue and a tail that is split: a 64 x 48 frame is all tail
         out.append(_leg(name, "persistent", option="large", size=LARGE, n_seeds=1, frames=FRAMES[1:]))
+    out += [_plan_leg(plan, cell) for cell in pm.PLAN_CELLS for plan in pm.PLANS]  # (a cell's plans share their expectation)
     return out
 
 

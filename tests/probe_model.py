@@ -15,7 +15,9 @@ So for every ray that meets occupied space: pixel rgb == the fp16 value of the c
 sample, bit for bit, and alpha == 1.  Hidden activation ReLU (rgb = relu(s v)) or None (rgb = s v); rgb output None.
 
 LEGS lists what the GPU file renders and the CPU file proves its conditions for.  FOG_LEGS (at the end): the same models with a
-thin density, whose frames show the compositor (test_fog_cpu.py, test_fog_gpu.py)."""
+thin density, whose frames show the compositor (test_fog_cpu.py, test_fog_gpu.py).  The "plan matrix" legs of both lists
+(PLAN_CELLS) are the ones that run the hot instance under its three static gather plans in every march form: the legs built
+on T12 never do (test_plan_matrix_cpu.py)."""
 from __future__ import annotations
 
 import numpy as np
@@ -50,6 +52,7 @@ def random_density_grid(H, cascade, seed, occupied=0.03):
 
 _BUILT = {}
 NGP_AABB32 = "instant-ngp, aabb_scale 32"
+BASE_PLS = "base.json: 2048 / 16 over 15 levels at bound 1"
 
 
 def _build(build_kw):
@@ -66,6 +69,8 @@ def resolve(build_kw):
     kw = dict(build_kw)
     if kw.get("per_level_scale") == NGP_AABB32:
         kw["per_level_scale"] = nh.default_per_level_scale(32.0, 16, 16)
+    if kw.get("per_level_scale") == BASE_PLS:
+        kw["per_level_scale"] = nh.default_per_level_scale(1.0, 16, 16)
     return kw
 
 
@@ -136,7 +141,9 @@ def probe_desc(build_kw, routes, density_grid=None, seed=0, sigma_weight=11.0):
 
 def pos01(xyz, bound):
     """World position -> [0, 1]: the one statement kernel (nrf_render.h sample_pos01) and oracle (network_one) share, in fp32:
-    the product by float(1 / (2 bound)) rounded, then + 0.5 rounded."""
+    the product by float(1 / (2 bound)) rounded, then + 0.5 rounded -- two roundings.  Where 1 / (2 bound) is a power of two
+    the product is exact and the kernel's single fma gives the same value; where it is not (bound 1.5: float(1 / 3)) the
+    kernel takes the multiply-then-add branch, which is this statement.  expected_rgb's assertion judges it against the oracle."""
     w = np.float32(1.0 / (2.0 * float(bound)))
     return (w * np.asarray(xyz, np.float32)).astype(np.float32) + np.float32(0.5)
 
@@ -145,9 +152,11 @@ def dir01(d):
     return (np.float32(0.5) * np.asarray(d, np.float32)).astype(np.float32) + np.float32(0.5)
 
 
-def expected_values(oracle, xyz, dirs, info):
-    """act(s * f16 encoding value) of the three routes at world positions / directions, float32 [n][3]."""
-    feat = oracle.encode_grid(pos01(xyz, info["bound"])).view(np.float16).astype(np.float32)
+def expected_values(oracle, xyz, dirs, info, feat=None):
+    """act(s * f16 encoding value) of the three routes at world positions / directions, float32 [n][3].  feat: grid features to
+    show in place of the oracle's (test_plan_matrix_cpu.py: what a wrong gather would put there)."""
+    if feat is None:
+        feat = oracle.encode_grid(pos01(xyz, info["bound"])).view(np.float16).astype(np.float32)
     dirf = oracle.encode_dir(dir01(dirs)).view(np.float16).astype(np.float32)
     want = np.empty((len(feat), 3), np.float32)
     for c, (kind, k, sign) in enumerate(info["routes"]):
@@ -204,6 +213,55 @@ STRIP, PERSISTENT = {"NRF_PERSISTENT": "0"}, {"NRF_PERSISTENT": "1"}
 GATHER = {"none": ({"NRF_QUAD_BUDGET_MB": "0"}, 0, 128), "near": ({}, 256, 80), "far": ({}, 6000, 56)}
 NO_GATHER_AXIS = {"-": ({}, 0, None)}
 
+# The plan matrix: base.json's grid (2^19 entries, 16 levels, F = 2, base resolution 16) with per_level_scale pinned to its
+# value at bound 1, so that the split between dense and hashed levels (0..4 dense) and with it the steps' forms do not move
+# with the bound: without copies {dense, mixed, hashed, hashed}, with 256 MB {quad, quad, hashed, hashed}, with 6000 MB
+# {quad, quad, far quad, hashed} -- the three static plans of the hot persistent kernel (csrc/nrf_launch.h), which no T12 model
+# reaches without copies and no loader-scaled bound-4 model reaches at 256 MB.  x four march cells.  Everything restated
+# here (plan ids, step forms, march forms, whether the march tables can live in LDS) is held to what the library reports by
+# test_plan_matrix_cpu.py.
+T19 = dict(log2_hashmap_size=19, H=32, per_level_scale=BASE_PLS)
+GFORM_MIXED, GFORM_DENSE, GFORM_HASHED, GFORM_QUAD, GFORM_QUAD_FAR = range(5)  # step forms (csrc/nrf_launch.h); the tests' one copy
+FORM_GENERIC, FORM_UNIT, FORM_POW2 = 0, 1, 2  # csrc/nrf_launch.h: MARCH_FORM_*
+# plan -> (GATHER key, the four steps' forms)
+PLANS = {
+    "dmhh": ("none", (GFORM_DENSE, GFORM_MIXED, GFORM_HASHED, GFORM_HASHED)),
+    "qqhh": ("near", (GFORM_QUAD, GFORM_QUAD, GFORM_HASHED, GFORM_HASHED)),
+    "qqfh": ("far", (GFORM_QUAD, GFORM_QUAD, GFORM_QUAD_FAR, GFORM_HASHED)),
+}
+# cell -> (build_model keywords, march form, whether the grid has the coarse occupancy level the march tables in LDS need).
+# generic_h: a grid side that is no multiple of 4 has no coarse level, so NO march table is staged in LDS and the model
+# renders in the per-strip kernel, which selects the gather forms at run time: the cell holds the hot strip kernel to the
+# references at this table size and reaches no static-plan instance.  generic_b is the cell that runs the three
+# MARCH_GENERIC static-plan instances: 1 / (2 bound) is no power of two (pos01's two roundings), mip_bound = min(2^k, bound).
+PLAN_CELLS = {
+    "unit": (dict(H=32, cascade=1, bound=1.0), FORM_UNIT, True),
+    "pow2": (dict(H=32, cascade=3, bound=4.0), FORM_POW2, True),
+    "generic_h": (dict(H=30, cascade=1, bound=1.0), FORM_GENERIC, False),
+    "generic_b": (dict(H=32, cascade=2, bound=1.5), FORM_GENERIC, True),
+}
+# what a cell's legs share, whatever their plan (one expectation serves a cell's three plans): (start of the route
+# alternation, density grid of the probe legs, fog route set)
+PLAN_CELL_MODELS = {"unit": (0, None, 21), "pow2": (1, "random", 22), "generic_h": (0, "random", 23), "generic_b": (1, None, 24)}
+
+
+def plan_id(forms):
+    """gather_plan() of csrc/nrf_launch.h"""
+    return 0x10000 | forms[0] | forms[1] << 4 | forms[2] << 8 | forms[3] << 12
+
+
+def plan_fields(plan, cell):
+    """What a plan-matrix leg adds to a leg: the plan and forms nrf_debug_gather_plan must report, the march form, and whether
+    the persistent kernel -- the static-plan instances' -- can run it."""
+    kw, form, tables = PLAN_CELLS[cell]
+    return dict(plan=plan, cell=cell, forms=PLANS[plan][1], plan_id=plan_id(PLANS[plan][1]), march_form=form, lds_tables=tables)
+
+
+def plan_sched(cell):
+    """The kernel that renders a cell's legs.  Their environment asks for the persistent kernel in every cell (NRF_PERSISTENT=1);
+    the library gives it where the march tables fit LDS, the per-strip kernel where the grid has no coarse level."""
+    return "persistent" if PLAN_CELLS[cell][2] else "strip"
+
 # name -> (build_model keywords, own instance, stage instance, extra environment)
 INSTANCES = {
     "hot": ({}, HOT, HOT, {}),
@@ -237,9 +295,9 @@ GEOMETRIES = {
 OPTIONS = ("perturb5", "u8", "views3", "shard1of3")
 
 
-def _leg(name, kw, own, stage, env, gather, routes, grid, option=None):
+def _leg(name, kw, own, stage, env, gather, routes, grid, option=None, table=T12):
     genv, budget, addresses = dict(GATHER, **NO_GATHER_AXIS)[gather]
-    return dict(id=name, build_kw=dict(T12, **kw), own=own, stage=stage, env=dict(env, **genv), budget_mb=budget,
+    return dict(id=name, build_kw=dict(table, **kw), own=own, stage=stage, env=dict(env, **genv), budget_mb=budget,
                 addresses=addresses, routes=routes, density_grid=grid, option=option, full=False, n_poses=2)
 
 
@@ -270,6 +328,14 @@ def _legs():
     for form in ("none", "far"):
         out.append(dict(_leg(f"hot-full-{form}", {}, HOT, HOT, PERSISTENT, form, full_routes(32, 16), "random" if form == "far" else None),
                         full=True, n_poses=3))
+    # the plan matrix: the plan without copies (held to nothing before, and reduced_routes shows every level of its mixed
+    # step in both signs) in every march cell; the two copy plans in the cells no exact reference reached
+    # (cell by cell: a cell's plans render the same models, whose expectations are made once)
+    for cell in PLAN_CELLS:
+        for plan in ("dmhh", "qqhh", "qqfh") if cell in ("pow2", "generic_b") else ("dmhh",):
+            start, grid, _ = PLAN_CELL_MODELS[cell]
+            out.append(dict(_leg(f"plan-{plan}-{cell}", PLAN_CELLS[cell][0], HOT, HOT, PERSISTENT, PLANS[plan][0],
+                                 reduced_routes(16, 2, 16, start=start), grid, table=T19), **plan_fields(plan, cell)))
     return out
 
 
@@ -339,15 +405,15 @@ def fog_routes(L, F, dir_raw, n, frequency):
 
 
 def _fog_leg(family, name, iname, sched, gather, weight, n, frames=FOG_FRAMES, geometry=None, opts_kw=None, option=None, env=None,
-             same_as_plain=False, size=(FRAME_W, FRAME_H)):
+             same_as_plain=False, size=(FRAME_W, FRAME_H), table=T12, cell_kw=None):
     kw, own, stage, ienv = INSTANCES[iname]
-    kw = dict(kw, **(GEOMETRIES[geometry] if geometry else {}))
+    kw = dict(kw, **(GEOMETRIES[geometry] if geometry else {}), **(cell_kw or {}))
     feat_raw, _, _, _, _, dir_raw, _ = syn.network_shape(syn.base_config(**INSTANCES[iname][0]))
     F = kw.get("n_features_per_level", 2)
     routes = fog_routes(feat_raw // F, F, dir_raw, n, kw.get("dir_otype") == "Frequency")
     genv, budget, addresses = dict(GATHER, **NO_GATHER_AXIS)[gather]
     sched_env = PERSISTENT if sched == "persistent" else STRIP
-    return dict(id=f"fog-{family}-{name}", family=family, instance=iname, sched=sched, gather=gather, build_kw=dict(T12, **kw),
+    return dict(id=f"fog-{family}-{name}", family=family, instance=iname, sched=sched, gather=gather, build_kw=dict(table, **kw),
                 own=own, stage=stage, env=dict(ienv, **sched_env, **genv, **(env or {})), plain_env=dict(ienv, **sched_env, **genv),
                 budget_mb=budget, addresses=addresses if geometry is None else None, routes=routes,
                 weight=float(weight), frames=tuple(frames), opts_kw=dict(opts_kw or {}), option=option, same_as_plain=same_as_plain,
@@ -386,6 +452,17 @@ def _fog_legs():
         out.append(_fog_leg("output", opt, "hot", "persistent", "near", W3, hot_n, option=opt, same_as_plain=True))
     for sched in ("persistent", "strip"):
         out.append(_fog_leg("large", sched, "hot", sched, "near", W3, hot_n, size=FOG_LARGE))
+    # the plan matrix: every plan in every march cell; in the cells with several cascades also max_steps 7 and 9 -- rounds that
+    # are no multiple of 16 samples, passes of one tile and of two, where a weight-fragment prefetch of the wrong depth shows.
+    # "u8planes": the frame once more into 8-bit planes (the OUT_U8 instances) == nrf_quantize_u8 of the float frame
+    for cell, (cell_kw, _, _) in PLAN_CELLS.items():
+        n_routes = PLAN_CELL_MODELS[cell][2]
+        for max_steps in (None, 7, 9) if cell in ("pow2", "generic_b") else (None,):
+            for plan, (gather, _) in PLANS.items():
+                out.append(dict(_fog_leg("plan", f"{plan}-{cell}" + (f"-max_steps{max_steps}" if max_steps else ""), "hot", "persistent",
+                                         gather, W3, n_routes, opts_kw=dict(max_steps=max_steps) if max_steps else None,
+                                         option="u8planes" if max_steps is None and cell != "generic_h" else None, table=T19,
+                                         cell_kw=cell_kw), sched=plan_sched(cell), **plan_fields(plan, cell)))
     return out
 
 

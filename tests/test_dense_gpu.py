@@ -13,7 +13,10 @@ each change at least half of them.
 What stays at a tolerance, for a stated reason: the uncertified hit pixels (1 .. 4 % of a frame, a direction value or hidden
 activation next to zero: two fp32 summation orders may round apart) keep mlp_close's relative bound without its absolute
 term, 4 * 2^-11 |want| plus one fp16 ulp of want; the sine / cosine columns of a Frequency model hold zero weights
-(v_sin_f32 against sinf, tests/test_probe_gpu.py); sigma of the stage kernels == fp16(exp(g0)) to rtol 2e-3 (v_exp_f32)."""
+(v_sin_f32 against sinf, tests/test_probe_gpu.py); sigma of the stage kernels == fp16(exp(g0)) to rtol 2e-3 (v_exp_f32).
+
+The "dense-plan-" legs (dense_model._plan_leg) render base.json's 2^19 table under each static gather plan in every march cell:
+the encodings read in the plan's forms in front of both MLPs, the plan asserted before the frame, the addresses after it."""
 import numpy as np
 import pytest
 
@@ -26,7 +29,7 @@ import nerfhip as nh  # noqa: E402
 import oracle_py as op  # noqa: E402
 import probe_model as pm  # noqa: E402
 import synthetic as syn  # noqa: E402
-from test_probe_gpu import _composited_close, _context, _instance, _plan  # noqa: E402
+from test_probe_gpu import _assert_plan, _composited_close, _context, _instance, _plan  # noqa: E402
 
 
 def _fp16_ulp(x):
@@ -76,7 +79,7 @@ def _check_frame(what, rgba, depth, exp, covered=None):
 
 @pytest.mark.parametrize("leg", dm.DENSE_LEGS, ids=[leg["id"] for leg in dm.DENSE_LEGS])
 def test_dense_frames_show_both_mlps_exactly(leg):
-    persistent = leg["sched"] == "persistent"
+    persistent = leg["sched"] == "persistent"  # (what runs: pm.plan_sched for the plan-matrix legs)
     runs = leg["own"] if persistent else leg["stage"]  # (instances other than the stage ones have the persistent form only)
     allow_own = int(leg["env"].get("NRF_WIDTH_INSTANCES", "1"))
     budget = int(leg["env"].get("NRF_QUAD_BUDGET_MB", leg["budget_mb"] or 8192))
@@ -95,9 +98,13 @@ def test_dense_frames_show_both_mlps_exactly(leg):
             d.gather_copy_budget_mb = leg["budget_mb"]
             ctx.load_model(d)
             # the instance meant is the one that runs
-            own, stage, _, _, _, _ = _plan(d, allow_own, budget)
+            own, stage, mask, far, _, _ = _plan(d, allow_own, budget)
             assert (own, stage) == (leg["own"], leg["stage"])
             assert _instance(ctx) == pm.INSTANCE_CLASS[runs] + (16 if persistent else 0), (leg["id"], _instance(ctx))
+            if "plan" in leg:  # the plan matrix: the static plan meant, read in the form meant
+                _assert_plan(ctx, d, leg)
+                assert (far != 0) == (leg["plan"] == "qqfh")
+                assert sum(2 if (mask >> level) & 1 else 8 for level in range(16)) == leg["addresses"]
             exp, what = _expectation(leg, seed, grid, p), (leg["id"], seed, grid)
             if option == "views3":
                 exps = [exp, _expectation(leg, seed, grid, 1 - p), exp]
@@ -111,6 +118,7 @@ def test_dense_frames_show_both_mlps_exactly(leg):
                 continue
             f = ctx.render(cam, poses[p])
             st = ctx.stats()
+            assert leg.get("addresses") in (None, st.gather_addresses_per_sample), (leg["id"], st.gather_addresses_per_sample)
             if option == "shard1of3":
                 tps = nh.tiles_per_shard(W, H, 3)
                 part, dpart = np.empty((f.n_tiles * 64, 4), np.float32), np.empty(f.n_tiles * 64, np.float32)

@@ -12,7 +12,11 @@ vacuously and that the bound sees a dropped sample, a stop threshold of 1e-3 and
 
 Measured worst error / bound (rgba and depth) per leg family on an MI355X, the oracle's own ratio on the same legs in brackets:
     strength 0.56 (0.56), instance 0.41 (0.41), option 0.40 (0.40), switch 0.34 (0.34), output 0.34 (0.34), large 0.37 (0.37);
-    chained nrf_composite: state 0.17, depth sum 0.22 (oracle 0.16 / 0.22).  `pytest -s` prints every frame's ratios."""
+    chained nrf_composite: state 0.17, depth sum 0.22 (oracle 0.16 / 0.22).  `pytest -s` prints every frame's ratios.
+
+The "fog-plan-" legs (probe_model.PLANS x PLAN_CELLS) run the hot instance's three static gather plans in every march cell, with
+max_steps 7 and 9 in the cascaded ones, and render the frame once more into 8-bit planes (the OUT_U8 instances), which must
+equal nrf_quantize_u8 of the float frame byte for byte."""
 import ctypes as C
 import os
 
@@ -27,6 +31,7 @@ import nerfhip as nh  # noqa: E402
 import oracle_py as op  # noqa: E402
 import probe_model as pm  # noqa: E402
 import synthetic as syn  # noqa: E402
+from test_probe_gpu import _assert_plan  # noqa: E402
 
 
 def _context(env):
@@ -158,7 +163,7 @@ def _plain_frames(leg, extra_pose):
 
 @pytest.mark.parametrize("leg", pm.FOG_LEGS, ids=[leg["id"] for leg in pm.FOG_LEGS])
 def test_fog_frames_stay_within_the_compositing_bound(leg):
-    persistent = leg["sched"] == "persistent"
+    persistent = leg["sched"] == "persistent"  # (what runs: pm.plan_sched for the plan-matrix legs)
     runs = leg["own"] if persistent else leg["stage"]  # (instances other than the stage ones have the persistent form only)
     allow_own = int(leg["env"].get("NRF_WIDTH_INSTANCES", "1"))
     budget = int(leg["env"].get("NRF_QUAD_BUDGET_MB", leg["budget_mb"] or 8192))
@@ -187,6 +192,8 @@ def test_fog_frames_stay_within_the_compositing_bound(leg):
             assert leg["addresses"] in (None, addresses)
             if leg["gather"] == "far":
                 assert far != 0 and (mask >> 8) & 15 == 15  # levels 8..11 come from far copies
+            if "plan" in leg:
+                _assert_plan(ctx, d, leg)
             if option == "views3":
                 ctx.set_max_views(3)
                 ctx.render_views(np.stack([cam] * 3), np.stack([pose, extra_pose, pose]))
@@ -239,6 +246,21 @@ def test_fog_frames_stay_within_the_compositing_bound(leg):
                 packed = (rgb8[..., 0].astype(np.uint32) | rgb8[..., 1].astype(np.uint32) << 8 | rgb8[..., 2].astype(np.uint32) << 16 |
                           d8.astype(np.uint32) << 24)
                 assert np.array_equal(got.cpu().numpy().view(np.uint32).reshape(H, W), packed)
+            if option == "u8planes":  # the OUT_U8 instance of the same plan and march form: its bytes == nrf_quantize_u8 of the float frame
+                n_px = W * H
+                src, dsrc = torch.from_numpy(rgba.reshape(-1, 4)).cuda(), torch.from_numpy(depth.reshape(-1)).cuda()
+                want8, wantd8 = torch.full((n_px, 3), 77, dtype=torch.uint8, device="cuda"), torch.full((n_px,), 78, dtype=torch.uint8, device="cuda")
+                got8, gotd8 = torch.full((n_px, 3), 79, dtype=torch.uint8, device="cuda"), torch.full((n_px,), 80, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                ctx.quantize_u8(src.data_ptr(), dsrc.data_ptr(), n_px, want8.data_ptr(), wantd8.data_ptr())
+                ctx.bind_output_u8(got8.data_ptr(), gotd8.data_ptr())
+                ctx.render(cam, pose)
+                st8 = ctx.stats()
+                torch.cuda.synchronize()
+                ctx.bind_output_u8(0, 0)
+                assert st8.n_composited == st.n_composited and st8.gather_addresses_per_sample == addresses, what
+                assert np.array_equal(got8.cpu().numpy(), want8.cpu().numpy()) and np.array_equal(gotd8.cpu().numpy(), wantd8.cpu().numpy()), what
+                assert len(np.unique(want8.cpu().numpy())) > 16  # (a picture: more byte values than a flat frame or a fill pattern holds)
     finally:
         ctx.close()
     print(f"fog-gpu-leg {leg['family']} {leg['id']}: worst error / bound {worst:.3f} (oracle {max(e['oracle_ratio'] for e in expectations):.3f})")

@@ -9,14 +9,10 @@ import pytest
 
 import models
 import nerfhip as nh
+from probe_model import GFORM_DENSE as DENSE, GFORM_HASHED as HASHED, GFORM_MIXED as MIXED, GFORM_QUAD as QUAD, GFORM_QUAD_FAR as QUAD_FAR  # step forms
+from probe_model import plan_id  # noqa: F401  (gather_plan() of csrc/nrf_launch.h)
 
-MIXED, DENSE, HASHED, QUAD, QUAD_FAR = range(5)  # step forms (csrc/nrf_launch.h)
 GATHER_RUNTIME = 0
-
-
-def plan_id(forms):
-    """gather_plan() of csrc/nrf_launch.h"""
-    return 0x10000 | forms[0] | forms[1] << 4 | forms[2] << 8 | forms[3] << 12
 
 
 QQFH = (QUAD, QUAD, QUAD_FAR, HASHED)

@@ -135,7 +135,7 @@ _ZN3nrf1bEv:
 
 # ---- which instances are compiled with the schedule
 
-FORM_GENERIC, FORM_UNIT, FORM_POW2 = 0, 1, 2  # csrc/nrf_launch.h: MARCH_FORM_*
+from probe_model import FORM_GENERIC, FORM_POW2, FORM_UNIT  # noqa: E402  (csrc/nrf_launch.h: MARCH_FORM_*)
 
 
 def lds_schedule(plan, form):

@@ -11,7 +11,10 @@ grid encoding against a float64 reference.
 The one exception, for a stated arithmetic reason: the direction channels of the Frequency legs (NET_WIDE).  The kernel
 evaluates the encoding with v_sin_f32 on arguments up to 2^11 pi, the oracle with libm's sinf (the reference itself uses
 __sinf); those channels keep the bound test_generic_gpu.py states for that instruction, 4e-3 absolute.  Their grid channels,
-and every channel of every other leg, are compared with array_equal."""
+and every channel of every other leg, are compared with array_equal.
+
+The "plan-" legs (probe_model.PLANS x PLAN_CELLS: base.json's 2^19 table) are the ones that run the hot instance's static gather
+plans; each asserts the plan and forms the library makes for its model before it renders (_assert_plan)."""
 import ctypes as C
 import os
 
@@ -56,6 +59,27 @@ def _plan(desc, allow_own, budget_mb):
 def _instance(ctx):
     ctx.lib.nrf_debug_instance.argtypes = [C.c_void_p]
     return ctx.lib.nrf_debug_instance(ctx.h)
+
+
+def _context_plan(ctx):
+    """The gather plan the context's loaded model launches with (a static plan's id, 0: the run-time selection)"""
+    fn = ctx.lib.nrf_debug_context_gather_plan
+    fn.argtypes, fn.restype = [C.c_void_p], C.c_longlong
+    return int(fn(ctx.h))
+
+
+def _assert_plan(ctx, desc, leg):
+    """A plan-matrix leg (pm.PLANS x pm.PLAN_CELLS), before it renders: the loaded model plans the static gather plan and the
+    step forms meant, at the budget the context plans with, and the kernel that runs is the persistent one -- the static-plan
+    instances' -- except in the cell whose grid has no coarse level: that one renders in the per-strip kernel."""
+    fn = ctx.lib.nrf_debug_gather_plan
+    fn.argtypes, fn.restype = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint32)], C.c_int
+    out = (C.c_uint32 * 5)()
+    budget = int(leg["env"].get("NRF_QUAD_BUDGET_MB", leg["budget_mb"])) or 1  # (0 would ask for the default budget: 1 MB grants no copy)
+    assert "NRF_GATHER_PLAN" not in os.environ and fn(C.byref(desc), 1, budget, out) == nh.NRF_OK
+    assert (int(out[0]), tuple(out[1:])) == (leg["plan_id"], leg["forms"]), (leg["id"], hex(out[0]), tuple(out[1:]))
+    assert _instance(ctx) == (16 if leg["lds_tables"] else 0), (leg["id"], _instance(ctx))
+    assert _context_plan(ctx) == leg["plan_id"], (leg["id"], hex(_context_plan(ctx)))  # what the loaded context launches with
 
 
 _EXPECTED = {}
@@ -108,7 +132,8 @@ def _composited_close(got, want):
 
 @pytest.mark.parametrize("leg", pm.LEGS, ids=[leg["id"] for leg in pm.LEGS])
 def test_probe_frames_show_the_encoding_exactly(leg):
-    persistent = leg["env"]["NRF_PERSISTENT"] == "1"
+    # (a grid without the coarse level has no march tables in LDS: the per-strip kernel renders it, pm.PLAN_CELLS generic_h)
+    persistent = leg["env"]["NRF_PERSISTENT"] == "1" and leg.get("lds_tables", True)
     runs = leg["own"] if persistent else leg["stage"]  # (instances other than the stage ones have the persistent form only)
     allow_own = int(leg["env"].get("NRF_WIDTH_INSTANCES", "1"))
     budget = int(leg["env"].get("NRF_QUAD_BUDGET_MB", leg["budget_mb"] or 8192))
@@ -133,8 +158,10 @@ def test_probe_frames_show_the_encoding_exactly(leg):
             nearest = leg["build_kw"].get("interpolation") == "Nearest"
             addresses = sum(2 if (mask >> level) & 1 else (1 if nearest else 8) for level in range(info["n_levels"]))
             assert leg["addresses"] in (None, addresses)
-            if leg["id"].endswith("-far"):
+            if leg["id"].endswith("-far") or leg.get("plan") == "qqfh":
                 assert far != 0 and (mask >> 8) & 15 == 15  # levels 8..11 come from far copies
+            if "plan" in leg:
+                _assert_plan(ctx, d, leg)
             what = (leg["id"], i)
             if option == "views3":
                 views = poses + [poses[0]]
