@@ -301,6 +301,39 @@ int nrf_render_batch(nrf_context* ctx, int n_views, const float* cams, const flo
  * fused kernel render with the exact arithmetic.  The arrays must stay valid until the call has completed.          */
 int nrf_render_rays(nrf_context* ctx, int n_views, const void* rays_o, const void* rays_d,
                     uint64_t rays_per_view, void* stream, nrf_frame* out);
+/* (ABI 7, addition) nrf_render_rays between per-ray limits of t, over a per-ray background: what a renderer needs to mix a
+ * NeRF into a scene of its own -- a ray stops at the depth of the geometry it hits (t_max), may start behind a portal or a
+ * near clip surface (t_min), and is composited over what lies behind it (background: the shaded geometry).
+ * rays_o, rays_d, rays_per_view: as nrf_render_rays.  t_min, t_max: device fp32 [n_views][rays_per_view], background: device
+ * fp32 [n_views][rays_per_view][3]; view v's entries start at v * rays_per_view in every array; NULL each: no limit / the
+ * scalar bg_color.  With all three NULL and flags 0 this IS nrf_render_rays (which calls it so), bit for bit.
+ * Limits.  A ray the guard accepts gets near, far as in nrf_render_rays (the aabb, min_near), then
+ *     if (t_min > near) near = t_min;   if (t_max < far) far = t_max;
+ * in exactly this form: a NaN limit is no limit, +-inf is legal.  Everything downstream uses the clamped pair -- the march,
+ * and the depth normalisation of get_image_and_depth, (depth - near) / (far - near); the frame is what the reference's
+ * per-ray loop yields with those two numbers replaced.  A ray with near >= far after the clamp is the background: alpha 0,
+ * depth 0.  t is in units along d, which is NOT normalised (as in nrf_render_rays): for a hit at distance s along the ray
+ * pass t = s / |d|.
+ * Background.  A pixel whose ray has an entry is rgb[k] = c[k] + (1 - weight_sum) * background[ray][k] -- the two roundings
+ * of the scalar epilogue; so is the pixel of a ray the guard refuses or whose interval is empty (it shows its own entry).  A
+ * pixel without a ray (ray number >= rays_per_view) keeps the scalar bg_color.
+ * flags: NRF_RAYS_DEPTH_T -- the depth plane holds the accumulated sum of w * t as composited (kernel_composite_rays'
+ * state[1]; divide by alpha for the expected hit distance) instead of its normalised form; 0 for a ray without samples.
+ * With an 8-bit output bound (nrf_bind_output_rgbd8 / _u8) the flag is NRF_E_UNSUPPORTED.  reserved != 0 or an unknown flag:
+ * NRF_E_INVALID.  Everything else -- options, perturb, shards, views, bound outputs, streams, the calls in flight, stats,
+ * the ray guard -- is as nrf_render_rays has it; all arrays must stay valid until the call has completed.          */
+enum { NRF_RAYS_DEPTH_T = 1 }; /* nrf_rays.flags */
+typedef struct nrf_rays {
+  const void* rays_o;
+  const void* rays_d;
+  uint64_t rays_per_view;
+  const void* t_min;
+  const void* t_max;
+  const void* background;
+  uint32_t flags;
+  uint32_t reserved; /* = 0 */
+} nrf_rays;
+int nrf_render_rays_clipped(nrf_context* ctx, int n_views, const nrf_rays* rays, void* stream, nrf_frame* out);
 /* Binds caller-owned device buffers (e.g. a render buffer's RGBA plane or a
  * torch tensor) as the target of subsequent nrf_render calls: rgba float
  * [n_px][4], depth float [n_px], n_px as nrf_frame describes.  NULL, NULL

@@ -1397,6 +1397,9 @@ struct ProgressArgs {
 struct RayArgs {
   const float *o, *d;  // device [n_views][per_view][3]
   uint64_t per_view;
+  // nrf_render_rays_clipped (nullptr / 0: nrf_render_rays): per-ray limits of t [n_views][per_view], per-ray background [..][3], nrf_rays.flags
+  const float *t_min = nullptr, *t_max = nullptr, *background = nullptr;
+  uint32_t flags = 0;
 };
 // The model as the RAYS instances see it: the persistent form for the hot shape only (nrf_context::rays_persistent); the per-strip
 // kernel borrows the weight area for the dilated table, so it is given what fits there (as set_density_grid decides without the
@@ -1456,6 +1459,10 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
       P.rays_o = rays->o + 3 * (size_t)first * rays->per_view;
       P.rays_d = rays->d + 3 * (size_t)first * rays->per_view;
       P.rays_per_view = (unsigned)rays->per_view;
+      P.ray_tmin = rays->t_min ? rays->t_min + (size_t)first * rays->per_view : nullptr;
+      P.ray_tmax = rays->t_max ? rays->t_max + (size_t)first * rays->per_view : nullptr;
+      P.ray_bg = rays->background ? rays->background + 3 * (size_t)first * rays->per_view : nullptr;
+      P.ray_flags = rays->flags;
     }
     for (int v = 0; !rays && v < VB.n_views; ++v) {
       nerf_matrix_to_ngp(poses + 16 * (size_t)(first + v), c->desc.scale, VB.v[v].R, VB.v[v].org);
@@ -1554,17 +1561,34 @@ int nrf_render_views(nrf_context* c, int n_views, const float* cams, const float
   return render_frames(c, n_views, cams, poses, nullptr, stream, out);
 }
 
-int nrf_render_rays(nrf_context* c, int n_views, const void* rays_o, const void* rays_d, uint64_t rays_per_view, void* stream,
-                    nrf_frame* out) {
+int nrf_render_rays_clipped(nrf_context* c, int n_views, const nrf_rays* r, void* stream, nrf_frame* out) {
   static const float none[16] = {};  // (check_renderable's null test is for cameras)
   int rc = check_renderable(c, none, none, n_views);
   if (rc) return rc;
-  if (!rays_o || !rays_d) return fail(NRF_E_INVALID, "null argument");
-  if (rays_per_view < 1 || rays_per_view > (uint64_t)c->W * (uint64_t)c->H)
+  if (!r || !r->rays_o || !r->rays_d) return fail(NRF_E_INVALID, "null argument");
+  if (r->reserved != 0 || (r->flags & ~(uint32_t)NRF_RAYS_DEPTH_T) != 0)
+    return fail(NRF_E_INVALID, "nrf_rays: reserved must be 0 and flags may hold NRF_RAYS_DEPTH_T only");
+  if (r->rays_per_view < 1 || r->rays_per_view > (uint64_t)c->W * (uint64_t)c->H)
     return fail(NRF_E_INVALID, "rays_per_view must be 1 .. width * height of nrf_set_resolution");
   if (c->opt.perturb > 0) return fail(NRF_E_UNSUPPORTED, "nrf_render_rays has no perturb instances (nrf_options.perturb must be 0)");
-  const RayArgs rays{(const float*)rays_o, (const float*)rays_d, rays_per_view};
+  if ((r->flags & NRF_RAYS_DEPTH_T) && (c->bound_rgbd8 || c->bound_rgb8))
+    return fail(NRF_E_UNSUPPORTED, "NRF_RAYS_DEPTH_T needs a float depth plane: an 8-bit output is bound");
+  RayArgs rays{(const float*)r->rays_o, (const float*)r->rays_d, r->rays_per_view};
+  rays.t_min = (const float*)r->t_min;
+  rays.t_max = (const float*)r->t_max;
+  rays.background = (const float*)r->background;
+  rays.flags = r->flags;
   return render_frames(c, n_views, nullptr, nullptr, &rays, stream, out);
+}
+
+int nrf_render_rays(nrf_context* c, int n_views, const void* rays_o, const void* rays_d, uint64_t rays_per_view, void* stream,
+                    nrf_frame* out) {
+  nrf_rays r;  // no limits, the scalar background, normalised depth
+  std::memset(&r, 0, sizeof(r));
+  r.rays_o = rays_o;
+  r.rays_d = rays_d;
+  r.rays_per_view = rays_per_view;
+  return nrf_render_rays_clipped(c, n_views, &r, stream, out);
 }
 
 // ---- host frames: the reference's render_frame ends in HOST memory (R/src/nerf_render.cu:345-359: D2H of the float

@@ -230,7 +230,15 @@ struct FrameParams {
   const float* rays_o;
   const float* rays_d;
   unsigned rays_per_view;
+  // nrf_render_rays_clipped: per-ray limits of t and a per-ray background, indexed like the rays (fp32 [n_views][rays_per_view] /
+  // [..][3], of the launch's view 0); nullptr each: no limit / the scalar bg_color.  ray_flags: NRF_RAYS_DEPTH_T = the depth plane
+  // holds the accumulated sum of w * t instead of its normalised form.  Read by the RAYS instances alone, at run time (wave-uniform).
+  unsigned ray_flags;
+  const float* ray_tmin;
+  const float* ray_tmax;
+  const float* ray_bg;
 };
+constexpr unsigned RAY_FLAG_DEPTH_T = 1u;  // == NRF_RAYS_DEPTH_T
 
 // ------------------------------------------------------------- ray guard ----
 // The march of render_utils.h:593-653 never ends once t + dt == t in fp32: with dt_min = 0.0034 that is t ~ 2^24 dt ~ 5.7e4 (the

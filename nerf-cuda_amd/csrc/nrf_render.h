@@ -1014,6 +1014,47 @@ __device__ __forceinline__ bool load_ray(const FrameParams& P, int view, uint32_
   return ok;
 }
 
+// nrf_render_rays_clipped: the caller's limits of t for ray rn of view `view` (FrameParams::ray_tmin / ray_tmax; the ray has passed
+// load_ray, so rn < rays_per_view), applied to what near_far gave it -- in exactly this form, so that a NaN limit is no limit.
+// Everything downstream (occupied-box clip, visibility walk, fast-forward, march, tail-split mail, depth epilogue) sees the clamped
+// pair only: the march holds for any near (min_near already moves it) and for any smaller far_m.
+__device__ __forceinline__ void clamp_ray(const FrameParams& P, int view, uint32_t rn, float& near, float& far) {
+  const size_t i = (size_t)view * P.rays_per_view + rn;
+  if (P.ray_tmin != nullptr) {  // (wave-uniform)
+    const float t_min = P.ray_tmin[i];
+    if (t_min > near) near = t_min;
+  }
+  if (P.ray_tmax != nullptr) {
+    const float t_max = P.ray_tmax[i];
+    if (t_max < far) far = t_max;
+  }
+}
+
+// get_image_and_depth, R/include/nerf-cuda/render_utils.h:257-264 (depth 0 when the ray missed the aabb): a finished ray's pixel.
+// RAYS: `listed` = the pixel has a ray in the caller's arrays (number rn of view `view`) -- such a pixel is composited over its own
+// entry of FrameParams::ray_bg when there is one (12 bytes, read here and carried nowhere), every other over the scalar bg_color;
+// RAY_FLAG_DEPTH_T: the depth is acc.dep as composited, not normalised.
+template <bool RAYS>
+__device__ __forceinline__ float4 finish_pixel(const FrameParams& P, const TileAcc& acc, float near, float far, int view, uint32_t rn,
+                                               bool listed, float& dn) {
+  const float span = far - near;
+  dn = span > 0.0f ? fmaxf(acc.dep - near, 0.0f) / span : 0.0f;
+  if constexpr (RAYS) {
+    if (P.ray_flags & RAY_FLAG_DEPTH_T) dn = acc.dep;
+    if (P.ray_bg != nullptr) {  // (wave-uniform)
+      float b0 = P.bg_color, b1 = P.bg_color, b2 = P.bg_color;
+      if (listed) {
+        const float* b = P.ray_bg + 3 * ((size_t)view * P.rays_per_view + rn);
+        b0 = b[0]; b1 = b[1]; b2 = b[2];
+      }
+      const float T = 1 - acc.ws;
+      return make_float4(acc.cr + T * b0, acc.cg + T * b1, acc.cb + T * b2, acc.ws);
+    }
+  }
+  const float bgw = (1 - acc.ws) * P.bg_color;
+  return make_float4(acc.cr + bgw, acc.cg + bgw, acc.cb + bgw, acc.ws);
+}
+
 // ------------------------------------------------------- the render kernel ----
 // 256 threads, >= 4 waves per SIMD (four workgroups per CU, 39.9 KB of LDS each): caps the kernel at
 // 128 VGPRs.  Small workgroups matter: a workgroup's LDS and wave slots are only released when its
@@ -1101,7 +1142,10 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   else ray_dir(V.R, V.cam, px, py, d);
   float near, far;
   near_far(M.aabb, o, d, P.min_near, near, far);
-  if constexpr (RAYS) if (!has_ray) near = far = 3.402823466e+38f;  // (what near_far gives a ray that misses the aabb)
+  if constexpr (RAYS) {
+    if (!has_ray) near = far = 3.402823466e+38f;  // (what near_far gives a ray that misses the aabb)
+    else clamp_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, near, far);
+  }
   const float rdx = 1 / d[0], rdy = 1 / d[1], rdz = 1 / d[2];
   const MarchConst mc = march_const(M, P.dt_gamma);
   const int sx = __builtin_signbitf(d[0]) ? 0 : 1;  // copysignf(1, d) > 0: the far face of the cell
@@ -1230,7 +1274,6 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   tile_rounds<NET, COARSE_LDS, MARCH, false, false, PERTURB, RAYS>(M, P, mc, lm, coarse_lds, ctab_lds, lane, o, d, rdx, rdy, rdz, sx, sy, sz,
                                                                    far_m, t_skip, t, tc, alive, acc, ts, 0, nullptr, pix_idx, 0.f, 0.f, nullptr,
                                                                    view);
-  const float ws = acc.ws, dep = acc.dep, cr = acc.cr, cg = acc.cg, cb = acc.cb;
   const unsigned n_samples = ts.n_samples, n_rounds = ts.n_rounds, n_tile_slots = ts.n_tile_slots;
   const unsigned n_composited = ts.n_composited;
 #ifdef NRF_PHASE_TIMING
@@ -1238,12 +1281,12 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   const unsigned n_lane_trips = ts.n_lane_trips, n_wave_iters = ts.n_wave_iters;
 #endif
 
-  // ---- get_image_and_depth, R/include/nerf-cuda/render_utils.h:257-264 (depth 0 when the ray missed the aabb)
+  // ---- get_image_and_depth (finish_pixel)
   {
-    const float bgw = (1 - ws) * P.bg_color;
-    const float span = far - near;
-    const float dn = span > 0.0f ? fmaxf(dep - near, 0.0f) / span : 0.0f;
-    store_pixel(P, rgba, depth, k_local, lane, px, py, in_img, make_float4(cr + bgw, cg + bgw, cb + bgw, ws), dn);
+    const uint32_t rn = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
+    float dn;
+    const float4 c = finish_pixel<RAYS>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
+    store_pixel(P, rgba, depth, k_local, lane, px, py, in_img, c, dn);
   }
   counters += (blockIdx.x % COUNTER_SLOTS) * 16;  // see COUNTER_SLOTS
   if (lane == 0 && n_rounds != 0) {           // waves that never sampled (background) add nothing
@@ -1547,7 +1590,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     else ray_dir(V.R, V.cam, px, py, d);
     float near, far;
     near_far(M.aabb, o, d, P.min_near, near, far);
-    if constexpr (RAYS) if (!has_ray) near = far = 3.402823466e+38f;
+    if constexpr (RAYS) {
+      if (!has_ray) near = far = 3.402823466e+38f;
+      else clamp_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, near, far);
+    }
     const float rdx = 1 / d[0], rdy = 1 / d[1], rdz = 1 / d[2];
     const int sx = __builtin_signbitf(d[0]) ? 0 : 1;
     const int sy = __builtin_signbitf(d[1]) ? 0 : 1;
@@ -1620,10 +1666,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
       }
 #endif
     }
-    // ---- get_image_and_depth, R/include/nerf-cuda/render_utils.h:257-264
-    const float bgw = (1 - acc.ws) * P.bg_color;
-    const float span = far - near;
-    float dn = span > 0.0f ? fmaxf(acc.dep - near, 0.0f) / span : 0.0f;
+    // ---- get_image_and_depth (finish_pixel)
+    float dn;
+    const uint32_t rn = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
+    const float4 c = finish_pixel<RAYS>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
 #ifdef NRF_PHASE_TIMING
     if (P.march_budget == 4095) {  // diagnostic: the depth plane carries the tile's cost (cycles / 1e6) and start time instead
       NRF_STAMP(t_tile_end);
@@ -1639,11 +1685,10 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
 #endif
     const unsigned long long given_mask = __ballot(given);
     if (given_mask == 0ull) {
-      store_pixel<OUT8>(P, rgba, depth, k_local, lane, px, py, in_img, make_float4(acc.cr + bgw, acc.cg + bgw, acc.cb + bgw, acc.ws), dn);
+      store_pixel<OUT8>(P, rgba, depth, k_local, lane, px, py, in_img, c, dn);
     } else if (!given && (in_img || P.tile_major)) {  // a split tile: the rays this wave kept, lane by lane
       const bool pad = !in_img;  // (padding pixels of a shard's tile-major buffer are zero)
-      store_ray_pixel<OUT8>(P, rgba, depth, pix_idx, pad ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(acc.cr + bgw, acc.cg + bgw, acc.cb + bgw, acc.ws),
-                            pad ? 0.f : dn);
+      store_ray_pixel<OUT8>(P, rgba, depth, pix_idx, pad ? make_float4(0.f, 0.f, 0.f, 0.f) : c, pad ? 0.f : dn);
     }
     if constexpr (U8) if (tx < P.tiles_x) tile_written(P, view, ty, lane, 64u - (unsigned)__popcll(given_mask));
   }
@@ -1736,10 +1781,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const OutPlanes op = view_planes<OUT8>(P, rgba0, depth0, view, VB.view_stride_px);
     const bool store = mine && !given;
     if (store) {  // get_image_and_depth, as in the tile loop
-      const float bgw = (1 - acc.ws) * P.bg_color;
-      const float span = far - near;
-      const float dn = span > 0.0f ? fmaxf(acc.dep - near, 0.0f) / span : 0.0f;
-      store_ray_pixel<OUT8>(P, op.rgba, op.depth, pix_idx, make_float4(acc.cr + bgw, acc.cg + bgw, acc.cb + bgw, acc.ws), dn);
+      float dn;  // (a helped ray is one of the caller's list: it was alive)
+      const float4 c = finish_pixel<RAYS>(P, acc, near, far, view, RAYS ? ray_number(P, pix_idx) : 0u, true, dn);
+      store_ray_pixel<OUT8>(P, op.rgba, op.depth, pix_idx, c, dn);
     }
     if constexpr (U8) {  // (8-bit planes are row-major: the strip row of the rays' tile follows from a pixel index)
       const int row = __builtin_amdgcn_readfirstlane((int)(pix_idx / (uint32_t)P.W)) >> 3;

@@ -539,9 +539,21 @@ void NerfRender::generate_rays(Camera cam, Matrix4f pos, int threadid) {
 }
 
 Image NerfRender::render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view) {
+  return render_rays(rays_o, rays_d, rays_per_view, nullptr, nullptr, nullptr);
+}
+
+Image NerfRender::render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view, const void* t_min, const void* t_max,
+                              const void* background) {
   if (!m_have_network) throw std::runtime_error{"render_rays: no network loaded"};
   if (m_ctx.size() != 1) throw std::runtime_error{"render_rays: single-device renderers only (device groups do not take rays)"};
-  check(nrf_render_rays(m_ctx[0], 1, rays_o, rays_d, rays_per_view, nullptr, nullptr), "nrf_render_rays");
+  nrf_rays r{};
+  r.rays_o = rays_o;
+  r.rays_d = rays_d;
+  r.rays_per_view = rays_per_view;
+  r.t_min = t_min;
+  r.t_max = t_max;
+  r.background = background;
+  check(nrf_render_rays_clipped(m_ctx[0], 1, &r, nullptr, nullptr), "nrf_render_rays_clipped");
   const size_t n = (size_t)resolution[0] * resolution[1];
   m_rays_rgb.resize(3 * n);
   m_rays_depth.resize(n);

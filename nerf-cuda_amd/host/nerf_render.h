@@ -78,6 +78,13 @@ class NerfRender {
   // rays_per_view and rays the guard refuses are background.  Single-device renderers only (device groups are out of its
   // scope).  The Image is host memory of this object, valid until the next render_rays.
   Image render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view);
+  // ... between per-ray limits of t and over a per-ray background (nrf_render_rays_clipped): t_min / t_max are DEVICE fp32
+  // [rays_per_view] in units of t along the (not normalised) direction, background DEVICE fp32 [rays_per_view][3]; nullptr each:
+  // no limit / the renderer's background.  What a rasteriser passes to mix the NeRF into its scene: its G-buffer's hit distance
+  // as t_max, its shaded colour as background.  The Image's depth is the normalised one: the metric depth plane
+  // (NRF_RAYS_DEPTH_T) is a float plane an 8-bit Image cannot hold, and is reachable through the C call only.
+  Image render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view, const void* t_min, const void* t_max,
+                    const void* background);
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in
   // nrf_generate_density_grid); reload_network_from_file calls it for a snapshot that carries no density grid
   void generate_density_grid();

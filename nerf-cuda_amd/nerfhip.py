@@ -122,6 +122,21 @@ class HostFrame(C.Structure):
 
 
 NRF_HOST_RGB_ONLY = 1
+NRF_RAYS_DEPTH_T = 1  # nrf_rays.flags: the depth plane holds the accumulated sum of w * t, not its normalised form
+
+
+class Rays(C.Structure):
+    """nrf_rays: the rays of nrf_render_rays_clipped with their per-ray limits of t and background (device pointers; 0 = none)."""
+    _fields_ = [
+        ("rays_o", C.c_void_p),
+        ("rays_d", C.c_void_p),
+        ("rays_per_view", C.c_uint64),
+        ("t_min", C.c_void_p),
+        ("t_max", C.c_void_p),
+        ("background", C.c_void_p),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
 
 
 class Stats(C.Structure):
@@ -175,6 +190,7 @@ _SIGS = {
     "nrf_render_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
                                    C.POINTER(Frame)]),
     "nrf_render_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Frame)]),
+    "nrf_render_rays_clipped": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Rays), C.c_void_p, C.POINTER(Frame)]),
     "nrf_read_view_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nrf_read_view_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nrf_bind_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -640,6 +656,19 @@ class NerfHip:
         f = Frame()
         _check(self.lib.nrf_render_rays(self.h, int(n_views), C.c_void_p(rays_o_ptr or 0), C.c_void_p(rays_d_ptr or 0),
                                         int(rays_per_view), C.c_void_p(stream or 0), C.byref(f)))
+        return f
+
+    def render_rays_clipped(self, rays_o_ptr, rays_d_ptr, rays_per_view: int, t_min_ptr=0, t_max_ptr=0, background_ptr=0,
+                            flags: int = 0, n_views: int = 1, stream=None) -> Frame:
+        """nrf_render_rays_clipped: render_rays between per-ray limits of t -- device fp32 [n_views][rays_per_view] each, in units
+        of t along the (not normalised) direction; a NaN entry, or a null pointer (0) for the whole array: no limit (an ENTRY of 0 is a
+        limit like any other: t_max = 0 empties the ray) -- over a per-ray background, device fp32
+        [n_views][rays_per_view][3] (0: the scalar bg_color).  flags: NRF_RAYS_DEPTH_T = the depth plane is the composited sum of
+        w * t (divide by alpha for the expected hit distance) instead of the normalised depth."""
+        r = Rays(rays_o_ptr or None, rays_d_ptr or None, int(rays_per_view), t_min_ptr or None, t_max_ptr or None,
+                 background_ptr or None, int(flags), 0)
+        f = Frame()
+        _check(self.lib.nrf_render_rays_clipped(self.h, int(n_views), C.byref(r), C.c_void_p(stream or 0), C.byref(f)))
         return f
 
     def read_view_f32(self, view: int):

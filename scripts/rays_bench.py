@@ -1,13 +1,17 @@
 """What rendering from caller-supplied rays costs against the pinhole path, on the flagship workload: the 1080p, T = 2^19
-base.json-shaped model in 16-view launches.  One process alternates three legs, so that all of them see the same box and clock:
+base.json-shaped model in 16-view launches.  One process alternates five legs, so that all of them see the same box and clock:
 
   views          nrf_render_views of 16 orbit cameras (code nrf_render_rays does not touch: the baseline)
   rays           nrf_render_rays on the nrf_generate_rays output of the same cameras, persistent RAYS instance
   rays_strip     the same through the per-strip RAYS instance (a context created under NRF_PERSISTENT=0)
+  rays_clipped   nrf_render_rays_clipped on the same rays with t_max = +inf in every entry and a background array that repeats
+                 bg_color: the limits limit nothing, so the leg prices the reads (4 + 12 B per ray) and renders the same frame
+  rays_clipped_strip   the same through the per-strip RAYS instance
+(--lib: another build of the library, e.g. the parent commit's; a build without nrf_render_rays_clipped runs the first three legs.)
 
 Per leg: device ms per view (hipEvents around the call's launches, nrf_stats.render_ms) -- median, minimum, maximum over the
 repetitions --, samples, and the shader clock the persistent kernel measured in its launches (0: the per-strip kernel has no such
-stamp).  The frames of the three legs are compared bit for bit first.  Prints one JSON object.
+stamp).  The frames of all legs are compared bit for bit first.  Prints one JSON object.
 
 Run it under a time limit:   timeout -k 10 300 python3 scripts/rays_bench.py [--reps 7] [--out profiles/.../rays_bench.json]"""
 import argparse
@@ -26,7 +30,17 @@ ap.add_argument("--views", type=int, default=16)
 ap.add_argument("--width", type=int, default=1920)
 ap.add_argument("--height", type=int, default=1080)
 ap.add_argument("--out", default=None)
+ap.add_argument("--lib", default=None, help="libnerfhip.so to measure (default: this tree's)")
+ap.add_argument("--legs", default=None, help="comma-separated subset of the legs (views is always run: it is the baseline); two "
+                "builds are compared with the SAME legs -- the clock a leg sees depends on what the process runs beside it")
 args = ap.parse_args()
+CLIPPED = True
+if args.lib:
+    import ctypes  # noqa: E402
+    nh.LIB_PATH = type(nh.LIB_PATH)(args.lib).resolve()
+    CLIPPED = hasattr(ctypes.CDLL(str(nh.LIB_PATH)), "nrf_render_rays_clipped")
+    if not CLIPPED:
+        del nh._SIGS["nrf_render_rays_clipped"]
 W, H, V = args.width, args.height, args.views
 cams = np.stack([syn.default_camera(W, H)] * V)
 poses = np.stack([syn.orbit_pose(360.0 * i / V, 30.0) for i in range(V)])
@@ -62,13 +76,24 @@ LEGS = {
     "rays_strip": lambda: cs.render_rays(rays_o.data_ptr(), rays_d.data_ptr(), W * H, n_views=V),
 }
 CTX = {"views": cp, "rays": cp, "rays_strip": cs}
+if CLIPPED:
+    t_max = torch.full((V, W * H), float("inf"), device="cuda")
+    bg = torch.full((V, W * H, 3), float(nh.default_options().bg_color), device="cuda")
+    torch.cuda.synchronize()
+    for name, c in (("rays_clipped", cp), ("rays_clipped_strip", cs)):
+        LEGS[name] = lambda c=c: c.render_rays_clipped(rays_o.data_ptr(), rays_d.data_ptr(), W * H, 0, t_max.data_ptr(),
+                                                        bg.data_ptr(), 0, n_views=V)
+        CTX[name] = c
+if args.legs:
+    LEGS = {k: f for k, f in LEGS.items() if k == "views" or k in args.legs.split(",")}
+    assert "rays" in LEGS, "the rays leg is the one the ratios are taken against"
 
-# the three legs render the same frames
+# all legs render the same frames
 frames = {}
 for name, run in LEGS.items():
     run()
     frames[name] = [CTX[name].read_view_f32(v) for v in (0, V // 2, V - 1)]
-for name in ("rays", "rays_strip"):
+for name in list(LEGS)[1:]:
     for a, b in zip(frames[name], frames["views"]):
         assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), name
 del frames
@@ -83,19 +108,23 @@ for _ in range(args.reps):
         ms[name].append(st.render_ms / V)
         clock[name].append(st.shader_clock_mhz)
         samples[name] = int(st.n_samples)
-res = {"workload": f"{V} views of {W}x{H}, T = 2^19 base.json shape", "reps": args.reps, "legs": {}}
+res = {"workload": f"{V} views of {W}x{H}, T = 2^19 base.json shape", "reps": args.reps, "lib": os.path.relpath(str(nh.LIB_PATH), ROOT), "legs": {}}
 for name in LEGS:
     a = np.array(ms[name])
     res["legs"][name] = {"ms_per_view_median": round(float(np.median(a)), 4), "ms_per_view_min": round(float(a.min()), 4),
                          "ms_per_view_max": round(float(a.max()), 4), "n_samples": samples[name],
                          "shader_clock_mhz": round(float(np.median(clock[name])), 1),
                          "ms_per_view_all": [round(float(x), 4) for x in a]}
-    print(f"{name:11s} {np.median(a):7.4f} ms/view (min {a.min():.4f}, max {a.max():.4f})  samples {samples[name]}  "
+    print(f"{name:18s} {np.median(a):7.4f} ms/view (min {a.min():.4f}, max {a.max():.4f})  samples {samples[name]}  "
           f"shader_clock_mhz {np.median(clock[name]):.0f}", file=sys.stderr, flush=True)
 m = {k: res["legs"][k]["ms_per_view_median"] for k in LEGS}
 spread = (res["legs"]["views"]["ms_per_view_max"] - res["legs"]["views"]["ms_per_view_min"]) / m["views"]
 res["rays_over_views"] = round(m["rays"] / m["views"], 4)
-res["rays_strip_over_rays"] = round(m["rays_strip"] / m["rays"], 4)
+for a, b in (("rays_strip", "rays"), ("rays_clipped", "rays"), ("rays_clipped_strip", "rays_strip")):
+    if a in m and b in m:
+        res[f"{a}_over_{b}"] = round(m[a] / m[b], 4)
+a = np.array(ms["rays"][1:] or ms["rays"])  # without the first repetition, which follows the read-back
+res["rays_run_to_run_spread"] = round(float((a.max() - a.min()) / np.median(a)), 4)
 res["views_run_to_run_spread"] = round(spread, 4)  # (max - min) / median of the baseline leg
 q1, q3 = np.percentile(np.array(ms["views"]), [25, 75])
 res["views_interquartile_spread"] = round(float((q3 - q1) / m["views"]), 4)
