@@ -2,6 +2,13 @@
 //   render_persistent_kernel<NET_HOT, march, .., RAYS>   the base.json shape whose march tables fit beside the persistent workgroup
 //   render_kernel<stage, .., RAYS>                       every other model (stage = NET_HOT, NET_WIDE, NET_GENERIC), and NRF_PERSISTENT=0
 // Exact arithmetic only: nrf_options::fast_interp is ignored here, perturb is refused by the entry point.
+// The 16 instances and the tests that launch each with a limit that limits (R = tests/test_render_rays_gpu.py, C =
+// tests/test_render_rays_clip_gpu.py: a grid of side 32; F = tests/test_render_rays_forms_gpu.py: the rows of tests/rays_forms.py):
+//   persistent hot   UNIT, POW2: float planes R C, UNIT 8-bit planes R C, POW2 8-bit planes F (bound4-cascade3);
+//                    GENERIC: float planes F (h96, h64-b1.5-c2, h128-b0.75, h48-b3-c3), 8-bit planes F (h64-b1.5-c2)
+//   per-strip hot    UNIT, POW2: R C;  GENERIC, tables in LDS: F (the same four rows);  tables in global memory: F (h30, h30-b4-c3)
+//   per-strip wide   UNIT: R C;  POW2: F (wide-pow2);  GENERIC, tables in LDS: F (wide-h96);  in global memory: F (wide-h30)
+//   per-strip generic   tables in LDS: R C (without a limit), F (sine-h96);  in global memory: F (sine-h30)
 // (one family of render-kernel instances per translation unit: nrf_render.h)
 #include "nrf_render.h"
 
