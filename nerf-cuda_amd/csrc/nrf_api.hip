@@ -20,6 +20,7 @@
 
 #include "nrf_device.h"
 #include "nrf_generic.h"
+#include "nrf_grid_plan.h"
 #include "nrf_launch.h"
 
 using namespace nrf;
@@ -235,6 +236,14 @@ void pack_generic_layer(const _Float16* Wm, uint32_t N, uint32_t K, std::vector<
         }
 }
 
+// bytes of the generic instance's weight fragments: pack_generic_layer's 1 KiB per 16 x 32 tile of every layer of the two MLPs
+uint32_t generic_frag_bytes(const nrf_model_desc& d, const GenModel& G) {
+  const uint32_t Wn = d.n_neurons;
+  auto tiles = [](uint32_t N, uint32_t K) { return (N / 16) * ((K + 31) / 32); };
+  auto mlp = [&](uint32_t in, uint32_t hidden) { return tiles(Wn, in) + (hidden - 1) * tiles(Wn, Wn) + tiles(16u, Wn); };
+  return 1024u * (mlp(G.feat_w, d.density_hidden_layers) + mlp(G.rgb_in, d.rgb_hidden_layers));
+}
+
 // R/include/nerf-cuda/render_utils.h:68-77
 // The descriptor checks of nrf_load_model that come before the old model is released: what the reference's vocabulary allows
 // (T/.../grid.h:1403-1411, T/src/fully_fused_mlp.cu:700-725, 653-655; spherical_harmonics.h:394-412); anything outside is
@@ -275,11 +284,6 @@ int validate_model(const nrf_model_desc& d, nrf_level_table& lv) {
   return NRF_OK;
 }
 
-// log2 of the side of the coarse occupancy blocks (4 x 4 x 4 cells per bit), 0 where the grid has none: a side that is no multiple
-// of 4.  Without the coarse level no march table is staged in LDS (set_density_grid) and the model renders in the per-strip
-// kernel, whatever its gather plan: the static-plan instances are the persistent kernel's (nrf_debug_march_form)
-inline uint32_t march_coarse_shift(uint32_t H) { return (H % 4 == 0 && H >= 8) ? 2u : 0u; }
-
 // What a model descriptor makes of the device side, decided without a device (nrf_debug_plan: tests/test_instance_plan_cpu.py).
 struct ModelPlan {
   int rc;                    // NRF_OK, or the refusal (fail() has set the message)
@@ -288,7 +292,7 @@ struct ModelPlan {
   GenModel gen;              // the generic description without its layers (valid unless stage == NET_HOT)
   uint32_t gen_wave_bytes;   // LDS bytes per wave of its direction + activation rows (0 when stage == NET_HOT)
   bool generic_grid;         // a level of LV_GENERIC index arithmetic
-  int own;                   // NET_*: the instance that renders the frames when its march tables fit (set_density_grid)
+  int own;                   // NET_*: the instance that renders the frames when its march tables fit (plan_grid)
   int stage;                 // NET_HOT, NET_WIDE or NET_GENERIC: the stage entry points, the per-strip kernel, the fallback
   uint32_t quad_mask, quad_far;  // DevModel::quad_mask / quad_far
   uint32_t uni_modes;        // DevModel::uni_modes
@@ -384,7 +388,7 @@ ModelPlan plan_model(const nrf_model_desc& d, bool allow_own, uint64_t budget_mb
   p.own = own;
   p.stage = own == NET_HOT || own == NET_WIDE ? own : NET_GENERIC;
   p.gen_wave_bytes = p.stage != NET_HOT ? gen_dir_bytes(G) + gen_act_bytes(G) : 0u;
-  if (p.stage == NET_GENERIC && render_gen_lds_fixed_bytes(p.gen_wave_bytes) > 160 * 1024) {
+  if (p.stage == NET_GENERIC && render_strip_lds_fixed_bytes(NET_GENERIC, p.gen_wave_bytes) > (int)CU_LDS_BYTES) {
     p.rc = fail(NRF_E_UNSUPPORTED, "HIP path: this network shape needs more LDS than a CU has");
     return p;
   }
@@ -493,8 +497,9 @@ struct nrf_context {
   void* d_ctab = nullptr;
   void* d_gen = nullptr;
   void* d_wfrag_gen = nullptr;  // wide models: generic-layout fragments for the stage entry points
-  bool rays_persistent = false; // nrf_render_rays runs the persistent RAYS instance (it exists for the hot shape only: set_density_grid), else the per-strip one
-  int own_net = NET_HOT;        // the loaded model's own instance (plan_model): set_density_grid checks for every grid whether it fits
+  GridFit fit{};                // what plan_grid made of the current density grid (fit.rays_persistent: nrf_render_rays runs the persistent RAYS instance)
+  size_t table_words[4] = {0, 0, 0, 0};  // words of d_occ, d_coarse, d_ctab, d_dilated
+  int own_net = NET_HOT;        // the loaded model's own instance (plan_model): plan_grid checks for every grid whether it fits
   void* d_wfrag_hot = nullptr;  // fragments of the model's own register-resident instance when it is not the stage one
   GenModel gen{};  // host copy of the generic instance's description (valid unless dm.stage == NET_HOT)
   std::vector<float> host_grid;  // the float density grid the march tables were built from
@@ -733,214 +738,93 @@ void view_roi(const float R[9], const float org[3], const float cam[4], const fl
   roi[3] = y1 < -1 ? -1 : (y1 > H - 1 ? H - 1 : (int)y1);
 }
 
-// Everything the march needs from the density grid (reference: the float grid [C*H^3] of load_snapshot,
-// nerf_render.cu:441-466, read by kernel_march_rays): occupancy bits, coarse occupancy, the box of occupied cells,
-// the dilated coarse sets of the visibility walk and the cell-boundary table.  Called by nrf_load_model with the
-// snapshot's grid and by nrf_generate_density_grid with the one evaluated from the network.  Needs c->desc, and
-// c->dm.stage / gen_wave_bytes (LDS budget of the tables) and c->own_net.
+// The grid side of the plan (nrf_grid_plan.h), decided without a device like plan_model (nrf_debug_grid_plan:
+// tests/test_grid_plan_cpu.py): the march tables of a density grid, which of them are staged in LDS, and the workgroup that
+// renders the frames beside them -- own / stage / gen_wave_bytes: plan_model's; gen_frag_bytes: DevModel's.
+struct GridPlan {
+  GridTables tables;
+  GridFit fit;
+};
+GridPlan plan_grid(const nrf_model_desc& d, int own, int stage, uint32_t gen_wave_bytes, uint32_t gen_frag_bytes, bool allow_persistent,
+                   bool allow_gen_wlds, const float* density_grid, float mean_density) {
+  GridPlan g;
+  g.tables = build_march_tables(d.density_grid_size, d.cascade, d.bound, d.aabb, density_grid, mean_density);
+  const int form = march_form(d.density_grid_size, d.cascade, d.bound);
+  auto candidate = [&](int net) {
+    FitCandidate k{net, {render_persist_waves(net, form), 0}, {0u, 0u}, net == NET_GENERIC, net == NET_HOT};
+    if (net == NET_GENERIC && k.waves[0] != 8) k.waves[1] = 8;
+    for (int s = 0; s < 2; ++s) k.lds_bytes[s] = k.waves[s] ? (uint32_t)render_persistent_lds_bytes(net, k.waves[s], gen_wave_bytes) : 0u;
+    return k;
+  };
+  FitInputs in{};
+  in.coarse_words = g.tables.coarse.size();
+  in.ctab_floats = g.tables.ctab.size();
+  in.dilated_words = g.tables.dilated.size();
+  in.own = candidate(own);
+  in.stage = candidate(stage);
+  in.stage_generic = stage == NET_GENERIC;
+  in.stage_wide = stage == NET_WIDE;
+  in.allow_persistent = allow_persistent;
+  in.allow_gen_wlds = allow_gen_wlds;
+  in.table_budget = (uint32_t)render_lds_table_max_bytes();
+  in.strip_fixed_bytes = (uint32_t)render_strip_lds_fixed_bytes(stage, gen_wave_bytes);
+  in.weight_area_bytes = (uint32_t)render_weight_area_bytes();
+  in.staged_weight_bytes = (uint32_t)render_staged_weight_bytes(gen_frag_bytes);
+  g.fit = fit_grid(in);
+  return g;
+}
+
+// the plan's part of DevModel (the table pointers are the caller's)
+void apply_grid_plan(DevModel& M, const GridPlan& g) {
+  for (int i = 0; i < 6; ++i) M.occ_box[i] = g.tables.occ_box[i];
+  M.coarse_shift = g.tables.coarse_shift;
+  M.dilated_level_words = g.tables.dilated_level_words;
+  M.lds_coarse_words = g.fit.lds_coarse_words;
+  M.lds_ctab_floats = g.fit.lds_ctab_floats;
+  M.lds_dilated_words = g.fit.persistent ? g.fit.lds_dilated_persist : g.fit.lds_dilated_strip;
+  M.net = (uint32_t)g.fit.net;
+  M.persistent = g.fit.persistent;
+  M.persist_waves = g.fit.persist_waves;
+  M.gen_weights_lds = g.fit.gen_weights_lds;
+}
+
+// Plans the march tables of a density grid (plan_grid) and uploads them.  Called by nrf_load_model with the snapshot's grid and
+// by nrf_generate_density_grid with the one evaluated from the network.  Needs c->desc, c->dm.stage / gen_wave_bytes /
+// gen_frag_bytes and c->own_net.
 int set_density_grid(nrf_context* c, const float* density_grid, float mean_density) {
-  const nrf_model_desc* d = &c->desc;
-  const uint64_t Hh = d->density_grid_size;
-  const uint64_t cells = Hh * Hh * Hh * d->cascade;
   HIP_TRY(hipDeviceSynchronize());  // nothing may still be marching on the old tables
   for (void** q : {&c->d_occ, &c->d_coarse, &c->d_ctab, &c->d_dilated}) {
     if (*q) (void)hipFree(*q);
     *q = nullptr;
   }
-  // occupancy bitfield: grid[cell] > min(0.01, mean_density) (render_utils.h:560,619), decided once
-  const float thresh = fminf(0.01f, mean_density);
-  std::vector<uint32_t> occ((cells + 31) / 32 + 1, 0u);
-  for (uint64_t i = 0; i < cells; ++i)
-    if (density_grid[i] > thresh) occ[i >> 5] |= 1u << (i & 31);
-
-  // march tables (nrf_device.h march_next): coarse occupancy = OR over 4x4x4 cell blocks, and the
-  // cell-boundary table ((v/(H-1))*2-1)*mip_bound in the reference's fp32 operation order
-  const uint32_t Hs = d->density_grid_size, Cs = d->cascade;
-  const uint32_t coarse_shift = march_coarse_shift(Hs);
-  std::vector<uint32_t> coarse;
-  if (coarse_shift) {
-    const uint32_t Hc = Hs >> 2;
-    coarse.assign(((uint64_t)Cs * Hc * Hc * Hc + 31) / 32 + 1, 0u);
-    for (uint64_t i = 0; i < cells; ++i) {
-      if (!((occ[i >> 5] >> (i & 31)) & 1u)) continue;
-      const uint32_t level = (uint32_t)(i / (Hh * Hh * Hh));
-      const uint64_t r = i % (Hh * Hh * Hh);
-      const uint32_t nx = (uint32_t)(r / (Hh * Hh)), ny = (uint32_t)((r / Hh) % Hh), nz = (uint32_t)(r % Hh);
-      const uint64_t cc = (((uint64_t)level * Hc + (nx >> 2)) * Hc + (ny >> 2)) * Hc + (nz >> 2);
-      coarse[cc >> 5] |= 1u << (cc & 31);
-    }
-  }
-  // A density cell of cascade k >= 1 is only ever looked up for positions of level k, i.e. with
-  // max|p| >= 2^(k-1) (kernel_march_rays picks the level from frexp(max|p|), render_utils.h:603-607): cells
-  // that lie, with one cell of slack, wholly inside the inner cube max|p| < 2^(k-1) cannot produce a sample
-  // whatever their value, so they count neither for the box of occupied cells nor for the visibility sets.
-  auto reachable = [&](uint32_t level, uint32_t nx, uint32_t ny, uint32_t nz) {
-    if (level == 0 || Cs <= 1) return true;
-    const double mb = fmin(ldexp(1.0, (int)level), (double)d->bound), cell = 2.0 * mb / (double)Hs;
-    const uint32_t n3[3] = {nx, ny, nz};
-    double r_max = 0.0;
-    for (int a = 0; a < 3; ++a) {
-      const double lo = -mb + n3[a] * cell, hi = lo + cell;
-      r_max = fmax(r_max, fmax(fabs(lo), fabs(hi)));
-    }
-    return !(r_max + cell < ldexp(1.0, (int)level - 1));
-  };
-  // world-space box around every occupied (and reachable) cell, inflated by 2 cells of its cascade level
-  float occ_box[6] = {1.f, 1.f, 1.f, -1.f, -1.f, -1.f};  // empty
-  bool boundary_occupied = false;  // an occupied (reachable) cell with index 0 or H-1 on some axis
-  {
-    bool any = false;
-    for (uint32_t level = 0; level < Cs; ++level) {
-      uint32_t lo[3] = {Hs, Hs, Hs}, hi[3] = {0, 0, 0};
-      bool lvl_any = false;
-      for (uint64_t r = 0; r < Hh * Hh * Hh; ++r) {
-        const uint64_t i = (uint64_t)level * Hh * Hh * Hh + r;
-        if (!((occ[i >> 5] >> (i & 31)) & 1u)) continue;
-        const uint32_t n3[3] = {(uint32_t)(r / (Hh * Hh)), (uint32_t)((r / Hh) % Hh), (uint32_t)(r % Hh)};
-        if (!reachable(level, n3[0], n3[1], n3[2])) continue;
-        for (int a = 0; a < 3; ++a) { lo[a] = n3[a] < lo[a] ? n3[a] : lo[a]; hi[a] = n3[a] > hi[a] ? n3[a] : hi[a]; }
-        lvl_any = true;
-      }
-      if (!lvl_any) continue;
-      const double mip_bound = fmin(Cs > 1 ? ldexp(1.0, (int)level) : 1.0, (double)d->bound);
-      const double cell = 2.0 * mip_bound / (double)Hs;
-      for (int a = 0; a < 3; ++a) {
-        float wlo = (float)(-mip_bound + ((double)lo[a] - 2.0) * cell);
-        float whi = (float)(-mip_bound + ((double)hi[a] + 3.0) * cell);
-        // The march clamps the position to +-bound and then the cell index to [0, H-1] (render_utils.h:595-611):
-        // a position OUTSIDE this cascade's cube -- bound > 2^(C-1), or an aabb wider than +-bound -- lands in the
-        // boundary layer of cells.  An occupied boundary cell therefore stands for everything beyond that face: the
-        // box is extended to wherever a ray can be (its aabb range) on that side.
-        if (lo[a] == 0) wlo = fminf(wlo, fminf(d->aabb[a], -d->bound) - (float)(2.0 * cell));
-        if (hi[a] == Hs - 1) whi = fmaxf(whi, fmaxf(d->aabb[a + 3], d->bound) + (float)(2.0 * cell));
-        if (!any || wlo < occ_box[a]) occ_box[a] = wlo;
-        if (!any || whi > occ_box[a + 3]) occ_box[a + 3] = whi;
-        boundary_occupied = boundary_occupied || lo[a] == 0 || hi[a] == Hs - 1;
-      }
-      any = true;
-    }
-  }
-  // Positions outside the outermost cube exist when bound > its mip_bound or the aabb is wider than +-bound.  The
-  // per-cascade visibility walk (coarse_visibility) only covers a ray's stretch INSIDE each cube, so with an
-  // occupied boundary layer in such a model it would miss those samples: the walk is switched off then (the box
-  // test above stays exact).
-  bool exterior_positions = false;
-  {
-    const float outer = fminf(Cs > 1 ? ldexpf(1.0f, (int)Cs - 1) : 1.0f, d->bound);
-    exterior_positions = d->bound > outer;
-    for (int a = 0; a < 3; ++a) exterior_positions = exterior_positions || d->aabb[a] < -d->bound || d->aabb[a + 3] > d->bound;
-  }
-  const bool visibility_walk = !(exterior_positions && boundary_occupied);
-  // Conservative coarse visibility set (single cascade): coarse cells that contain, or lie within one
-  // density cell of, an occupied density cell (= the coarse image of the occupancy dilated by one
-  // fine cell); used by the per-ray DDA of render_kernel (nrf_device.h coarse_visibility).
-  std::vector<uint32_t> dilated;
-  uint32_t dilated_level_words = 0;  // words per cascade level (whole words, so a level's bits start at bit 0)
-  if (coarse_shift && visibility_walk) {
-    const int Hc = (int)(Hs >> 2), Hf = (int)Hs;
-    dilated_level_words = (uint32_t)(((uint64_t)Hc * Hc * Hc + 31) / 32);
-    dilated.assign((size_t)dilated_level_words * Cs, 0u);
-    for (uint32_t level = 0; level < Cs; ++level) {
-      uint32_t* dl = dilated.data() + (size_t)level * dilated_level_words;
-      for (int x = 0; x < Hf; ++x)
-        for (int y = 0; y < Hf; ++y)
-          for (int z = 0; z < Hf; ++z) {
-            const uint64_t i = (((uint64_t)level * Hf + x) * Hf + y) * Hf + z;
-            if (!((occ[i >> 5] >> (i & 31)) & 1u)) continue;
-            if (!reachable(level, (uint32_t)x, (uint32_t)y, (uint32_t)z)) continue;
-            for (int dx = -1; dx <= 1; ++dx)
-              for (int dy = -1; dy <= 1; ++dy)
-                for (int dz = -1; dz <= 1; ++dz) {
-                  const int X = x + dx, Y = y + dy, Z = z + dz;
-                  if (X < 0 || Y < 0 || Z < 0 || X >= Hf || Y >= Hf || Z >= Hf) continue;
-                  const uint64_t nn = ((uint64_t)(X >> 2) * Hc + (Y >> 2)) * Hc + (Z >> 2);
-                  dl[nn >> 5] |= 1u << (nn & 31);
-                }
-          }
-    }
-  }
-  std::vector<float> ctab((size_t)Cs * (Hs + 1));
-  for (uint32_t level = 0; level < Cs; ++level) {
-    const float mip_bound = fminf(Cs > 1 ? ldexpf(1.0f, (int)level) : 1.0f, d->bound);
-    const float Hm1 = (float)(Hs - 1);
-    for (uint32_t v = 0; v <= Hs; ++v) ctab[(size_t)level * (Hs + 1) + v] = ((float)v / Hm1 * 2 - 1) * mip_bound;
-  }
-
-  auto upload = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(dst, bytes);
+  DevModel& M = c->dm;
+  const GridPlan g = plan_grid(c->desc, c->own_net, (int)M.stage, M.gen_wave_bytes, M.gen_frag_bytes, c->allow_persistent, c->allow_gen_wlds,
+                               density_grid, mean_density);
+  const GridTables& T = g.tables;
+  auto upload = [&](void** dst, const void* src, size_t words) -> hipError_t {  // (a table the grid does not have stays null)
+    if (words == 0) return hipSuccess;
+    hipError_t e = hipMalloc(dst, words * 4);
     if (e != hipSuccess) return e;
-    return hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+    return hipMemcpyAsync(*dst, src, words * 4, hipMemcpyHostToDevice, c->stream);
   };
-  HIP_TRY(upload(&c->d_occ, occ.data(), occ.size() * 4));
-  if (coarse_shift) HIP_TRY(upload(&c->d_coarse, coarse.data(), coarse.size() * 4));
-  HIP_TRY(upload(&c->d_ctab, ctab.data(), ctab.size() * 4));
-  if (!dilated.empty()) HIP_TRY(upload(&c->d_dilated, dilated.data(), dilated.size() * 4));
+  const size_t n_words[4] = {T.occ.size(), T.coarse.size(), T.ctab.size(), T.dilated.size()};
+  HIP_TRY(upload(&c->d_occ, T.occ.data(), n_words[0]));
+  HIP_TRY(upload(&c->d_coarse, T.coarse.data(), n_words[1]));
+  HIP_TRY(upload(&c->d_ctab, T.ctab.data(), n_words[2]));
+  HIP_TRY(upload(&c->d_dilated, T.dilated.data(), n_words[3]));
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipDeviceSynchronize());
-  DevModel& M = c->dm;
   M.occ_bits = (const uint32_t*)c->d_occ;
-  for (int i = 0; i < 6; ++i) M.occ_box[i] = occ_box[i];
   M.occ_coarse = (const uint32_t*)c->d_coarse;
   M.cell_bound = (const float*)c->d_ctab;
   M.occ_dilated = (const uint32_t*)c->d_dilated;
-  M.coarse_shift = coarse_shift;
-  M.lds_coarse_words = M.lds_ctab_floats = M.lds_dilated_words = 0;
-  {
-    const uint64_t words = coarse_shift ? (uint64_t)coarse.size() : 0, fl = ctab.size();
-    uint64_t budget = (uint64_t)render_lds_table_max_bytes();
-    if (M.stage == NET_GENERIC) {  // whatever the generic instance's rows leave of the CU's 160 KiB
-      const uint64_t used = (uint64_t)render_gen_lds_fixed_bytes(M.gen_wave_bytes);
-      budget = used + budget <= 160u * 1024u ? budget : 160u * 1024u - used;
-    }
-    if (M.stage == NET_WIDE) {  // three workgroups per CU: (160 KiB / 3 - fixed part) for the tables
-      const uint64_t room = 160u * 1024u / 3u - (uint64_t)render_wide_lds_fixed_bytes();
-      budget = budget < room ? budget : room;
-    }
-    if (coarse_shift && 4 * (words + fl) <= budget) {
-      M.lds_coarse_words = (uint32_t)words;
-      M.lds_ctab_floats = (uint32_t)fl;
-    }
-  }
-  M.dilated_level_words = dilated_level_words;
-  if (!dilated.empty() && dilated.size() * 4 <= (size_t)N_FRAGS * 64 * 16) M.lds_dilated_words = (uint32_t)dilated.size();
-  // The persistent form of the render kernel (one workgroup per CU, waves pull strips from work queues) keeps every march
-  // table in LDS for the whole launch: tables that fit beside the blocks of its waves.  The model's own instance if they fit
-  // beside its workgroup (a register-resident instance other than the stage one has the persistent form only), else the
-  // stage instance -- the generic one with 12 waves and its weight fragments in LDS, 12 without, 8 with, 8 without: the first
-  // that fits (NRF_GEN_WLDS=0 at nrf_create: never stage the fragments).  Decided again for every grid (nrf_generate_density_grid).
-  M.net = M.stage;
-  M.persistent = 0;
-  M.persist_waves = 0;
-  M.gen_weights_lds = 0;
   M.n_cus = (uint32_t)c->n_cus;
-  if (c->allow_persistent && M.lds_coarse_words > 0) {
-    const size_t tables = 4 * ((size_t)M.lds_coarse_words + M.lds_ctab_floats + dilated.size());
-    const int form = march_form(M.H, M.cascade, M.bound);
-    for (const int net : {c->own_net, (int)M.stage}) {
-      const int first_waves = render_persist_waves(net, form);
-      for (int waves : {first_waves, net == NET_GENERIC && first_waves != 8 ? 8 : 0}) {  // (only the generic instance has a second size)
-        if (waves == 0 || M.persistent) break;
-        const size_t fixed = (size_t)render_persistent_lds_bytes(net, waves, M.gen_wave_bytes) + tables;
-        for (int wlds : {1, 0}) {
-          if (wlds && (net != NET_GENERIC || !c->allow_gen_wlds)) continue;
-          if (fixed + (wlds ? 16u + M.gen_frag_bytes : 0u) <= 160u * 1024u) {
-            M.net = (uint32_t)net;
-            M.persistent = 1;
-            M.persist_waves = (uint32_t)waves;
-            M.gen_weights_lds = (uint32_t)wlds;
-            M.lds_dilated_words = (uint32_t)dilated.size();
-            break;
-          }
-        }
-      }
-      if (M.persistent) break;
-    }
-  }
-  // caller-supplied rays (nrf_render_rays): the persistent RAYS instance is the hot shape's; every other model -- and a hot one
-  // whose tables do not fit -- renders rays in the per-strip RAYS instance of its stage (nrf_kernels_rays.hip)
-  c->rays_persistent = M.persistent != 0 && M.net == NET_HOT;
+  apply_grid_plan(M, g);
+  c->fit = g.fit;
+  std::copy(n_words, n_words + 4, c->table_words);
   c->desc.mean_density = mean_density;
-  c->host_grid.assign(density_grid, density_grid + cells);
+  const uint64_t Hh = c->desc.density_grid_size;
+  c->host_grid.assign(density_grid, density_grid + Hh * Hh * Hh * c->desc.cascade);
   return NRF_OK;
 }
 
@@ -1241,7 +1125,7 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   c->gather_addresses = 0;
   for (uint32_t l = 0; l < L; ++l) c->gather_addresses += ((quad_mask >> l) & 1u) ? 2u : (d->interpolation == NRF_INTERP_NEAREST ? 1u : 8u);
   M.stage = (uint32_t)p.stage;
-  M.net = (uint32_t)p.own;  // (set_density_grid falls back to the stage instance when the own one does not fit)
+  M.net = (uint32_t)p.own;  // (plan_grid falls back to the stage instance when the own one does not fit)
   c->own_net = p.own;
   M.gen = (const GenModel*)c->d_gen;
   M.gen_wave_bytes = p.gen_wave_bytes;
@@ -1401,16 +1285,14 @@ struct RayArgs {
   const float *t_min = nullptr, *t_max = nullptr, *background = nullptr;
   uint32_t flags = 0;
 };
-// The model as the RAYS instances see it: the persistent form for the hot shape only (nrf_context::rays_persistent); the per-strip
-// kernel borrows the weight area for the dilated table, so it is given what fits there (as set_density_grid decides without the
-// persistent form).
+// The model as the RAYS instances see it: the persistent form for the hot shape only (GridFit::rays_persistent); the per-strip
+// kernel borrows the weight area for the dilated table, so it is given what fits there (GridFit::lds_dilated_strip)
 DevModel rays_model(const nrf_context* c) {
   DevModel m = c->dm;
-  if (!c->rays_persistent) {
+  if (!c->fit.rays_persistent) {
     m.persistent = 0;
     m.net = m.stage;
-    const size_t words = (size_t)m.dilated_level_words * m.cascade;
-    m.lds_dilated_words = m.occ_dilated != nullptr && words * 4 <= (size_t)N_FRAGS * 64 * 16 ? (uint32_t)words : 0u;
+    m.lds_dilated_words = c->fit.lds_dilated_strip;
   }
   return m;
 }
@@ -1960,7 +1842,7 @@ extern "C" int nrf_debug_instance(nrf_context* c) {
 // nrf_debug_instance (0 register-resident, 1 generic, 2 wide), + 16 for the persistent form (the hot shape whose tables fit)
 extern "C" int nrf_debug_rays_instance(nrf_context* c) {
   if (!c || !c->model_loaded) return -1;
-  if (c->rays_persistent) return 16;
+  if (c->fit.rays_persistent) return 16;
   const int st = (int)c->dm.stage;
   return st == NET_GENERIC ? 1 : st == NET_WIDE ? 2 : 0;
 }
@@ -2029,6 +1911,62 @@ extern "C" int nrf_debug_march_form(uint32_t H, uint32_t cascade, float bound, u
   if (!out || H == 0 || cascade == 0 || !(bound > 0.0f)) return fail(NRF_E_INVALID, "bad argument");
   out[0] = (uint32_t)march_form(H, cascade, bound);
   out[1] = march_coarse_shift(H) ? 1u : 0u;
+  return NRF_OK;
+}
+
+// the 17 values nrf_debug_grid_plan and nrf_debug_grid_readout share: the fit, the tables' geometry and their lengths in words
+static void grid_plan_values(const DevModel& M, const GridFit& f, const size_t n_words[4], uint32_t out[17]) {
+  const uint32_t v[17] = {M.net, M.stage, M.persistent, M.persist_waves, M.gen_weights_lds, M.lds_coarse_words, M.lds_ctab_floats, f.lds_dilated_strip,
+                          f.lds_dilated_persist, M.coarse_shift, M.dilated_level_words, f.rays_persistent ? 1u : 0u,
+                          M.persistent ? (uint32_t)render_persistent_launch_lds_bytes(M) : 0u,  // (what launch_render asks for)
+                          (uint32_t)n_words[0], (uint32_t)n_words[1], (uint32_t)n_words[2], (uint32_t)n_words[3]};
+  std::memcpy(out, v, sizeof(v));
+}
+
+// Diagnostic (not part of include/nerfhip.h): plan_model, then plan_grid, of a descriptor without a device -- grid: [C * H^3] floats
+// (null: the descriptor's), flags: bit 0 allow_own (NRF_WIDTH_INSTANCES), bit 1 allow_persistent (NRF_PERSISTENT), bit 2 allow_gen_wlds
+// (NRF_GEN_WLDS); reads no environment.  out = {net, stage, persistent, persist_waves, gen_weights_lds, lds_coarse_words, lds_ctab_floats,
+// the dilated words staged by the per-strip and by the persistent form, coarse_shift, dilated_level_words, rays_persistent, the LDS
+// bytes launch_render asks for (from a DevModel the plan was applied to, as set_density_grid does), words of occ / coarse / ctab /
+// dilated, visibility_walk, GridFit::persistent_lds_bytes}; box = occ_box; the tables are copied to the buffers that are given
+// (tests/test_grid_plan_cpu.py)
+extern "C" int nrf_debug_grid_plan(const nrf_model_desc* d, const float* grid, float mean_density, uint32_t flags, uint32_t out[19], float box[6],
+                                   uint32_t* occ, uint32_t* coarse, float* ctab, uint32_t* dilated) {
+  if (!d || !d->params || !out || !box || (!grid && !d->density_grid)) return fail(NRF_E_INVALID, "null argument");
+  const ModelPlan p = plan_model(*d, (flags & 1u) != 0, QUAD_BUDGET_MB_DEFAULT, 4);
+  if (p.rc) return p.rc;
+  DevModel M;
+  std::memset(&M, 0, sizeof(M));
+  M.stage = (uint32_t)p.stage;
+  M.gen_wave_bytes = p.gen_wave_bytes;
+  M.gen_frag_bytes = p.stage == NET_GENERIC ? generic_frag_bytes(*d, p.gen) : 0u;
+  const GridPlan g = plan_grid(*d, p.own, p.stage, M.gen_wave_bytes, M.gen_frag_bytes, (flags & 2u) != 0, (flags & 4u) != 0,
+                               grid ? grid : d->density_grid, mean_density);
+  apply_grid_plan(M, g);
+  const GridTables& T = g.tables;
+  const size_t n_words[4] = {T.occ.size(), T.coarse.size(), T.ctab.size(), T.dilated.size()};
+  grid_plan_values(M, g.fit, n_words, out);
+  out[17] = T.visibility_walk ? 1u : 0u;
+  out[18] = g.fit.persistent_lds_bytes;
+  std::memcpy(box, T.occ_box, sizeof(T.occ_box));
+  if (occ) std::memcpy(occ, T.occ.data(), T.occ.size() * 4);
+  if (coarse) std::memcpy(coarse, T.coarse.data(), T.coarse.size() * 4);
+  if (ctab) std::memcpy(ctab, T.ctab.data(), T.ctab.size() * 4);
+  if (dilated) std::memcpy(dilated, T.dilated.data(), T.dilated.size() * 4);
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the same 17 values of the loaded context, its occ_box, and its four device tables
+// copied to the buffers that are given (tests/test_grid_plan_gpu.py)
+extern "C" int nrf_debug_grid_readout(nrf_context* c, uint32_t out[17], float box[6], uint32_t* occ, uint32_t* coarse, float* ctab,
+                                      uint32_t* dilated) {
+  if (!c || !c->model_loaded || !out || !box) return fail(NRF_E_INVALID, "bad argument");
+  grid_plan_values(c->dm, c->fit, c->table_words, out);
+  std::memcpy(box, c->dm.occ_box, sizeof(c->dm.occ_box));
+  void* dst[4] = {occ, coarse, ctab, dilated};
+  const void* src[4] = {c->d_occ, c->d_coarse, c->d_ctab, c->d_dilated};
+  for (int i = 0; i < 4; ++i)
+    if (dst[i] && c->table_words[i]) HIP_TRY(hipMemcpy(dst[i], src[i], c->table_words[i] * 4, hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

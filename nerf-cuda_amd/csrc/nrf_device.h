@@ -127,7 +127,7 @@ struct DevModel {
   uint32_t rgb_activation, rgb_output_activation;
   uint32_t uni_modes;    // 2 bits per unrolled step jl = 0..3 of the fused kernel (levels 4*jl + g): 0 mixed, 1 all dense,
                          // 2 all power-of-two hashed (host: nrf_load_model)
-  uint32_t net;          // NET_* (nrf_launch.h): the instance that renders the frames (set_density_grid: the model's own one when its
+  uint32_t net;          // NET_* (nrf_launch.h): the instance that renders the frames (nrf_api.hip plan_grid: the model's own one when its
                          // march tables fit beside its persistent workgroup, else `stage`)
   uint32_t stage;        // NET_HOT (the shape of the reference's base.json), NET_WIDE (the same with a Frequency direction encoding
                          // of 32..80 values) or NET_GENERIC (everything else, nrf_generic.h, described by `gen`): the instance of the

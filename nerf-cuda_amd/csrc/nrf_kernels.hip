@@ -753,6 +753,10 @@ static inline int grid_for(uint64_t n, int block = 256, int cap = 256 * 8) {
 }
 
 static int gen_lds_bytes(const DevModel& M, int waves) { return LDS_LEVEL_BYTES + waves * ((int)sizeof(WaveLds) + (int)M.gen_wave_bytes); }
+int render_strip_lds_fixed_bytes(int stage, uint32_t gen_wave_bytes) {  // the per-strip workgroup without march tables (what launch_render asks for, what plan_grid fits beside)
+  if (stage == NET_GENERIC) return LDS_LEVEL_BYTES + RENDER_WAVES * ((int)sizeof(WaveLds) + (int)gen_wave_bytes);
+  return stage == NET_WIDE ? LDS_FIXED_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + RENDER_WAVES * LDS_RAYD_BYTES : LDS_FIXED_BYTES;
+}
 
 hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBatch& VBin, void* rgba, void* depth, void* counters,
                          hipStream_t st, bool first_launch, unsigned* plan, unsigned plan_cap) {
@@ -803,8 +807,7 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     VB.class_cols = (strips_x + N - 1) / N;  // a row holds at most this many of the rank's strips
     if ((long long)q * VB.class_cols >= 0xffffff) return hipErrorInvalidValue;  // 24-bit queue positions
     const int waves = (int)M.persist_waves;
-    const int lds = render_persistent_lds_bytes((int)M.net, waves, M.gen_wave_bytes) + 4 * (int)(M.lds_coarse_words + M.lds_ctab_floats + M.lds_dilated_words) +
-                    (M.gen_weights_lds ? 16 + (int)M.gen_frag_bytes : 0);
+    const int lds = render_persistent_launch_lds_bytes(M);
     const long long tiles = (long long)P.n_local_tiles * VB.n_views;
     const int wgs = (int)std::max(1LL, std::min((long long)M.n_cus, (tiles + waves - 1) / waves));
     unsigned* queue = reinterpret_cast<unsigned*>((unsigned long long*)counters + COUNTER_SLOTS * 16);
@@ -838,10 +841,7 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     const hipError_t e0 = clear_for_first();
     if (e0 != hipSuccess) return e0;
   }
-  const int fixed = M.stage == NET_GENERIC ? gen_lds_bytes(M, RENDER_WAVES)
-                              : (M.stage == NET_WIDE ? LDS_FIXED_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + RENDER_WAVES * LDS_RAYD_BYTES
-                                        : LDS_FIXED_BYTES);
-  const int lds = fixed + (lds_tab ? 4 * (int)(M.lds_coarse_words + M.lds_ctab_floats) : 0);
+  const int lds = render_strip_lds_fixed_bytes((int)M.stage, M.gen_wave_bytes) + (lds_tab ? 4 * (int)(M.lds_coarse_words + M.lds_ctab_floats) : 0);
   // hot instances: compile-time activations, march tables in LDS; a power-of-two grid with either one cascade and
   // mip_bound == 1 (MARCH_UNIT) or several cascades and a power-of-two bound (MARCH_POW2)
   const int form = march_form(M.H, M.cascade, M.bound);
@@ -1084,9 +1084,14 @@ int render_persistent_lds_bytes(int net, int waves, uint32_t gen_wave_bytes) {
   const int wave_rows = net == NET_GENERIC ? (int)gen_wave_bytes : (net == NET_WIDE ? LDS_RAYD_BYTES : (net == NET_WIDE_SH ? LDS_SHROW_BYTES : 0));
   return (net == NET_GENERIC ? 0 : net_wfrag_bytes(net)) + LDS_LEVEL_BYTES + waves * ((int)sizeof(WaveLds) + wave_rows) + LDS_QUEUE_BYTES;
 }
-int render_wide_lds_fixed_bytes() { return LDS_FIXED_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + RENDER_WAVES * LDS_RAYD_BYTES; }
 int render_lds_table_max_bytes() { return LDS_MARCH_TABLE_MAX; }
-int render_gen_lds_fixed_bytes(uint32_t gen_wave_bytes) { return LDS_LEVEL_BYTES + RENDER_WAVES * ((int)sizeof(WaveLds) + (int)gen_wave_bytes); }
+int render_weight_area_bytes() { return LDS_WFRAG_BYTES; }
+int render_staged_weight_bytes(uint32_t gen_frag_bytes) { return 16 + (int)gen_frag_bytes; }
+int render_persistent_launch_lds_bytes(const DevModel& M) {
+  return (int)persistent_lds_total((uint32_t)render_persistent_lds_bytes((int)M.net, (int)M.persist_waves, M.gen_wave_bytes),
+                                   (uint64_t)M.lds_coarse_words + M.lds_ctab_floats + M.lds_dilated_words,
+                                   M.gen_weights_lds ? (uint32_t)render_staged_weight_bytes(M.gen_frag_bytes) : 0u);
+}
 
 
 }  // namespace nrf

@@ -4,10 +4,12 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "nrf_grid_plan.h"  // persistent_lds_total: the sum plan_grid and launch_render share
+
 namespace nrf {
 // Instances of the render kernel (nrf_render.h), one id for host and device code.  DevModel::net renders the frames;
 // DevModel::stage (NET_HOT, NET_WIDE or NET_GENERIC) runs the stage entry points, the per-strip kernel and the density-grid
-// generation, and renders the frames when the model's own instance does not fit (nrf_api.hip plan_model, set_density_grid).
+// generation, and renders the frames when the model's own instance does not fit (nrf_api.hip plan_model, plan_grid).
 // NET_W16 / NET_W32 / NET_W128: the register-resident instance for the other widths of tcnn's FullyFusedMLP (persistent kernel only)
 // NET_WIDE_SH: the wide form for SphericalHarmonics of degree 5..8 (32..64 direction values): the entries beyond the first sixteen
 // are computed once per ray into an LDS row (not per sample in-lane as for Frequency) -- persistent kernel only
@@ -85,7 +87,7 @@ hipError_t launch_untile_rgbd8_u8(const void* gathered, int shard_count, int til
                                   void* depth8, hipStream_t st);
 hipError_t launch_quantize_rgbd8(const void* rgba, const void* depth, uint64_t n, void* out, hipStream_t st);
 hipError_t launch_quantize(const void* rgba, const void* depth, int n, void* rgb8, void* depth8, hipStream_t st);
-// The march form of a model and the waves of its persistent workgroup: ONE rule, read by set_density_grid (which sizes the
+// The march form of a model and the waves of its persistent workgroup: ONE rule, read by plan_grid (nrf_api.hip; it sizes the
 // workgroup's LDS and decides whether the model fits the persistent kernel) and by launch_render (which picks the kernel
 // instance); the launch macros refuse a workgroup size other than their instance's.
 enum : int { MARCH_FORM_GENERIC = 0, MARCH_FORM_UNIT = 1, MARCH_FORM_POW2 = 2 };
@@ -114,13 +116,16 @@ __host__ __device__ constexpr bool plan_levels(uint32_t gp) { return gp != GATHE
 __host__ __device__ constexpr int plan_frag_depth(uint32_t gp, int march) {
   return gp == GATHER_RUNTIME ? 0 : (march == MARCH_FORM_GENERIC ? NRF_LDS_FRAG_DEPTH_GENERIC : NRF_LDS_FRAG_DEPTH);
 }
-// waves of the persistent workgroup of instance `net` with that march form (NET_GENERIC may also run with 8: set_density_grid
+// waves of the persistent workgroup of instance `net` with that march form (NET_GENERIC may also run with 8: plan_grid
 // tries 12 first), and its LDS bytes without the march tables (gen_wave_bytes: the generic instance's per-wave rows)
 int render_persist_waves(int net, int form);
 int render_persistent_lds_bytes(int net, int waves, uint32_t gen_wave_bytes);
 // loads the code objects of the render kernel's instance families now instead of at their first launch
 void preload_kernels(bool all);
-int render_lds_table_max_bytes();
-int render_wide_lds_fixed_bytes();  // wide instance: LDS of render_kernel without the march tables
-int render_gen_lds_fixed_bytes(uint32_t gen_wave_bytes);  // generic instance: LDS of render_kernel without the march tables
+// The LDS figures plan_grid (nrf_api.hip) fits the march tables with; launch_render sizes its launches from the same functions.
+int render_lds_table_max_bytes();  // coarse + cell-boundary tables beyond this stay in global memory
+int render_strip_lds_fixed_bytes(int stage, uint32_t gen_wave_bytes);  // LDS of the per-strip render_kernel of that stage instance without the march tables
+int render_weight_area_bytes();    // the per-strip kernel's weight area: it holds the dilated table during ray setup
+int render_staged_weight_bytes(uint32_t gen_frag_bytes);  // generic instance, persistent kernel: its weight fragments staged in LDS
+int render_persistent_launch_lds_bytes(const DevModel& M);  // LDS of the persistent launch of a model plan_grid found one for
 }  // namespace nrf
