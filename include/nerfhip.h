@@ -321,8 +321,21 @@ int nrf_render_rays(nrf_context* ctx, int n_views, const void* rays_o, const voi
  * state[1]; divide by alpha for the expected hit distance) instead of its normalised form; 0 for a ray without samples.
  * With an 8-bit output bound (nrf_bind_output_rgbd8 / _u8) the flag is NRF_E_UNSUPPORTED.  reserved != 0 or an unknown flag:
  * NRF_E_INVALID.  Everything else -- options, perturb, shards, views, bound outputs, streams, the calls in flight, stats,
- * the ray guard -- is as nrf_render_rays has it; all arrays must stay valid until the call has completed.          */
-enum { NRF_RAYS_DEPTH_T = 1 }; /* nrf_rays.flags */
+ * the ray guard -- is as nrf_render_rays has it; all arrays must stay valid until the call has completed.
+ * flags: NRF_RAYS_DENSITY_ONLY (ABI 7, addition; may be combined with NRF_RAYS_DEPTH_T) -- shadow and occlusion rays: how much
+ * light gets through and where, not what colour the volume has.  The density network alone is evaluated per sample; the
+ * direction encoding and the colour network are not.  Everything else is this call's, unchanged: the ray guard, near / far and
+ * the clamp, the march, its termination (T < 1e-4, max_steps, far) and density_scale, views, shards and tile_major, bound float
+ * outputs, streams and the 16 calls in flight, stats.  nrf_frame.rgba[..][3] (weight_sum), the depth plane and nrf_stats'
+ * n_rays / n_composited are bit-identical to the same call without the flag.  rgb of a pixel that has a ray is
+ *     rgb[k] = (1 - weight_sum) * b[k]      (fp32: the subtraction rounded, then the product rounded)
+ * with b the ray's entry of background, or the scalar bg_color when background is NULL -- the epilogue above with c = 0.  A ray
+ * the guard refuses or whose interval is empty after the clamp has alpha 0, depth 0 and rgb = its background entry; a pixel
+ * without a ray keeps bg_color, alpha 0, depth 0.  Use: pass the unshadowed radiance of the light as background and the distance
+ * to the light over |d| as t_max; rgb is the radiance that arrives, alpha the opacity in between.  With an 8-bit output bound
+ * (nrf_bind_output_rgbd8 / _u8) the flag is NRF_E_UNSUPPORTED.  The value is 4: bit 1 (value 2) stays unassigned and is, like
+ * every other unknown bit, NRF_E_INVALID.  nrf_render_rays and the pinhole entry points have no such mode.          */
+enum { NRF_RAYS_DEPTH_T = 1, NRF_RAYS_DENSITY_ONLY = 4 }; /* nrf_rays.flags */
 typedef struct nrf_rays {
   const void* rays_o;
   const void* rays_d;

@@ -1448,13 +1448,15 @@ int nrf_render_rays_clipped(nrf_context* c, int n_views, const nrf_rays* r, void
   int rc = check_renderable(c, none, none, n_views);
   if (rc) return rc;
   if (!r || !r->rays_o || !r->rays_d) return fail(NRF_E_INVALID, "null argument");
-  if (r->reserved != 0 || (r->flags & ~(uint32_t)NRF_RAYS_DEPTH_T) != 0)
-    return fail(NRF_E_INVALID, "nrf_rays: reserved must be 0 and flags may hold NRF_RAYS_DEPTH_T only");
+  if (r->reserved != 0 || (r->flags & ~(uint32_t)(NRF_RAYS_DEPTH_T | NRF_RAYS_DENSITY_ONLY)) != 0)
+    return fail(NRF_E_INVALID, "nrf_rays: reserved must be 0 and flags may hold NRF_RAYS_DEPTH_T and NRF_RAYS_DENSITY_ONLY only");
   if (r->rays_per_view < 1 || r->rays_per_view > (uint64_t)c->W * (uint64_t)c->H)
     return fail(NRF_E_INVALID, "rays_per_view must be 1 .. width * height of nrf_set_resolution");
   if (c->opt.perturb > 0) return fail(NRF_E_UNSUPPORTED, "nrf_render_rays has no perturb instances (nrf_options.perturb must be 0)");
   if ((r->flags & NRF_RAYS_DEPTH_T) && (c->bound_rgbd8 || c->bound_rgb8))
     return fail(NRF_E_UNSUPPORTED, "NRF_RAYS_DEPTH_T needs a float depth plane: an 8-bit output is bound");
+  if ((r->flags & NRF_RAYS_DENSITY_ONLY) && (c->bound_rgbd8 || c->bound_rgb8))
+    return fail(NRF_E_UNSUPPORTED, "NRF_RAYS_DENSITY_ONLY needs float planes: an 8-bit output is bound");
   RayArgs rays{(const float*)r->rays_o, (const float*)r->rays_d, r->rays_per_view};
   rays.t_min = (const float*)r->t_min;
   rays.t_max = (const float*)r->t_max;

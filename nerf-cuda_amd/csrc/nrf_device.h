@@ -239,6 +239,13 @@ struct FrameParams {
   const float* ray_bg;
 };
 constexpr unsigned RAY_FLAG_DEPTH_T = 1u;  // == NRF_RAYS_DEPTH_T
+// == NRF_RAYS_DENSITY_ONLY (bit 1 stays unassigned).  The host reads it to pick the launch's instances (nrf_kernels_rays.hip); no
+// kernel tests it: density-only is a compile-time mode of the RAYS instances, RAYS_DENSITY below.
+constexpr unsigned RAY_FLAG_DENSITY_ONLY = 4u;
+// The RAYS template argument of tile_rounds, render_kernel and render_persistent_kernel (nrf_render.h): where an instance's rays
+// come from and what it evaluates for a sample.  RAYS_DENSITY: the density network alone -- no direction encoding, no colour
+// network, no colour sums; alpha, depth and the statistics are those of RAYS_FULL bit for bit, rgb is the transmitted background.
+constexpr int RAYS_NONE = 0, RAYS_FULL = 1, RAYS_DENSITY = 2;
 
 // ------------------------------------------------------------- ray guard ----
 // The march of render_utils.h:593-653 never ends once t + dt == t in fp32: with dt_min = 0.0034 that is t ~ 2^24 dt ~ 5.7e4 (the
@@ -1247,12 +1254,16 @@ struct MlpOut {
 // D0_BASE .. D0_BASE + MT - 1, then S::D1 .. S::N - 1, and fragment f + PF is read from LDS before the MFMAs of fragment f issue,
 // across layer boundaries and repack(); `pre` = the first PF fragments, which the caller has read already.  The order is pinned
 // by scheduling barriers that LDS reads and MFMAs may not cross (everything else may); the waits stay the compiler's.
-template <int NT, int D0_BASE = FRAG_D0, typename Frags = LdsFrags, int RK = 1, int W = 64, int PF = 0>
+// DENS (the RAYS_DENSITY instances, nrf_render.h): the density MLP alone -- the fragments D0_BASE .. + MT - 1 and S::D1 .. + KS - 1,
+// one repack(); returns once out.sigma is complete, by the same instructions as the full form.  out.rg / out.bx are not written,
+// dirf / dirx are not read.
+template <int NT, int D0_BASE = FRAG_D0, typename Frags = LdsFrags, int RK = 1, int W = 64, int PF = 0, bool DENS = false>
 __device__ __forceinline__ void mlp_tiles(const Frags frag_lds, const half8_t (&feat)[NT], const half4_t (&dirf)[NT], MlpOut<NT>& out,
                                           bool rgb_sigmoid = false, const half8_t (*dirx)[RK_WIDE - 1] = nullptr,
                                           const half8_t* pre = nullptr) {
   static_assert(NT == 1 || NT == 2 || NT == 4, "tiles per pass");
   static_assert(PF == 0 || RK == 1, "the fragment prefetch covers the fragments 0 .. S::N - 1");
+  static_assert(!DENS || PF == 0, "the rolling prefetch runs through both MLPs");
   using S = MlpShape<W>;
   constexpr int MT = S::MT, KS = S::KS;
   half8_t wq[PF > 0 ? PF : 1];
@@ -1330,6 +1341,7 @@ __device__ __forceinline__ void mlp_tiles(const Frags frag_lds, const half8_t (&
   }
   // extract_density: fp32 activation (Exponential) of the fp16 density output, stored as fp16
   out.sigma = (half_t)expf((float)bits_h2(dall).x);
+  if constexpr (DENS) return;
   // ---- rgb layer 0: 32 (or 32 RK) -> W
 #pragma unroll
   for (int m = 0; m < MT; ++m) {

@@ -1072,6 +1072,7 @@ void preload_kernels(bool all) {
     preload_strip();
     preload_grid();
     preload_rays();
+    preload_rays_density();
   }
 }
 

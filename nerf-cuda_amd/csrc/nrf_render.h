@@ -106,6 +106,7 @@ __device__ __forceinline__ unsigned long long stamp_rt() {
 // The lane's 8 grid features (4 dwords) of a GRID instance: lane group g encodes the levels {g, 4 + g, ...} it can hold -- 4 levels
 // of F = 2, 2 of F = 4, 1 of F = 8 -- features in tcnn's order level-major; levels the grid does not have are zero (the padding of
 // the grid encoding is ZERO, grid.h:959-969).  K order of the first density layer: nrf_api.hip pack_fragments_grid.
+// DENS (the RAYS_DENSITY instances): sigma alone -- no read of dirf, rayd or rows, mlp_tiles<.., DENS>, no store of W->out[slot].xyz.
 // F = 1 (NET_GRID1, round 5): lane group g holds the ONE feature of each of its levels {g, 4 + g, 8 + g, 12 + g} -- four halves, the
 // lane's other four features are zero columns (feat_w = 16: pack_fragments_grid) --, two levels to a dword, two levels in flight.
 __device__ __forceinline__ void grid_features_f1(const DevModel& M, const LevelParams* lvs, float px, float py, float pz, int g, uint32_t (&fb)[4]) {
@@ -304,10 +305,11 @@ __device__ __forceinline__ void sample_pos01(const DevModel& M, const float4 p, 
 }
 
 template <int NT, int RK = 1, bool FAST = false, int WD = 64, bool SHROWS = false, int DEPTH = 0, int GF = 0, uint32_t GP = GATHER_RUNTIME,
-          int PF = 0>
+          int PF = 0, bool DENS = false>
 __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const float* rayd, int S, int base, int lane, float density_scale,
                                                  const half_t* rows = nullptr) {
+  static_assert(!DENS || (DEPTH == 0 && WD == 64 && PF == 0 && GF == 0 && !SHROWS), "density-only forms exist for the RAYS instances' stages");
   const int g = lane >> 4, c = lane & 15;
   half8_t feat[NT];
   half4_t dirf[NT];
@@ -377,7 +379,7 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
       }
       }
       const int ray = __builtin_bit_cast(int, p.w);
-      db = *reinterpret_cast<const uint2*>(&W->dirf[ray][2 * g]);
+      if constexpr (!DENS) db = *reinterpret_cast<const uint2*>(&W->dirf[ray][2 * g]);
       if constexpr (RK > 1 && SHROWS) {
         const half8_t z8 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
 #pragma unroll
@@ -385,12 +387,12 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
           const uint32_t e0 = 32u * s - 16u + 8u * (uint32_t)g;  // first direction entry of this lane's B fragment
           dirx[n][s - 1] = e0 < M.dir_w ? *reinterpret_cast<const half8_t*>(rows + (size_t)ray * SH_ROW_HALVES + e0) : z8;  // (zero weights beyond)
         }
-      } else if constexpr (RK > 1) {
+      } else if constexpr (RK > 1 && !DENS) {
         const float dx = rayd[3 * ray], dy = rayd[3 * ray + 1], dz = rayd[3 * ray + 2];
 #pragma unroll
         for (int s = 1; s < RK; ++s) dirx[n][s - 1] = dir_entries8(M.n_frequencies, 32u * s - 16u + 8u * (uint32_t)g, dx, dy, dz);
       }
-    } else if constexpr (RK > 1) {
+    } else if constexpr (RK > 1 && !DENS) {
       const half8_t z8 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
 #pragma unroll
       for (int s = 1; s < RK; ++s) dirx[n][s - 1] = z8;
@@ -414,13 +416,14 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
   if constexpr (DEPTH == 2) mlp_tiles_depth<NT, LdsFragsPlain, true>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, M.depth_xd,
                                                                      M.depth_xr, M.density_activation, M.rgb_activation);
   else if constexpr (DEPTH == 1) mlp_tiles_depth<NT>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, M.depth_xd, M.depth_xr);
+  else if constexpr (DENS) mlp_tiles<NT, FRAG_D0, LdsFrags, RK, 64, 0, true>(LdsFrags{wl, lane}, feat, dirf, o);
   else if constexpr (WD == 64 && PF > 0) {
     static_assert(RK == 1, "the fragment prefetch exists for the hot instance only");
     mlp_tiles<NT, FRAG_D0, LdsFrags, 1, 64, PF>(LdsFrags{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, nullptr, wpre);
   }
   else if constexpr (WD == 64) mlp_tiles<NT, FRAG_D0, LdsFrags, RK>(LdsFrags{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, dirx);
   else mlp_tiles<NT, 0, LdsFragsPlain, 1, WD>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID);
-  if (g == 0) {  // decompose_network_in_and_out (render_utils.h:308-334): fp16 rows 0..2 -> fp32 rgb
+  if (!DENS && g == 0) {  // decompose_network_in_and_out (render_utils.h:308-334): fp16 rows 0..2 -> fp32 rgb
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       const int slot = base + 16 * n + c;
@@ -489,7 +492,8 @@ __device__ __forceinline__ void gen_network_from_lds(const DevModel& M, const Ge
   gen_wave_sync();  // the next pass overwrites the rows
 }
 
-template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME, int PF = 0>
+// DENS: the density network alone (the RAYS_DENSITY instances)
+template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME, int PF = 0, bool DENS = false>
 __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const GenLds& Lw, int S, int lane, float density_scale) {
   constexpr int RK = (NET == NET_WIDE || NET == NET_WIDE_SH) ? RK_WIDE : 1;
@@ -497,7 +501,7 @@ __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4*
   if constexpr (NET == NET_GENERIC) {
     const GenModel& G = *M.gen;
     for (int base = 0; base < S; base += GEN_SAMPLES)  // wave-uniform
-      gen_network_from_lds<false>(M, G, lvs, W, Lw, S, base, lane, density_scale);
+      gen_network_from_lds<DENS>(M, G, lvs, W, Lw, S, base, lane, density_scale);
   } else {
     constexpr int WD = net_width(NET);
     constexpr int NTM = WD == 128 ? 1 : NT_MAX;  // 128 neurons: eight accumulator fragments per tile -- one tile per pass
@@ -505,8 +509,8 @@ __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4*
       const int ntile = (S - base + 15) >> 4;
       constexpr int DP = NET == NET_DEPTH ? 1 : (NET == NET_ACT ? 2 : 0);  // (2: runtime hidden activations)
       constexpr int GF = net_grid_f(NET);
-      if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF, GP, PF>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
-      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP, PF>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF, GP, PF, DENS>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP, PF, DENS>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
     }
   }
 }
@@ -798,7 +802,10 @@ __device__ __forceinline__ uint32_t ray_number(const FrameParams& P, uint32_t pi
 // the hot persistent instance (128 VGPR + AGPR at 16 waves), so a live lane re-reads its origin at the top of every round's march --
 // the only phase that uses it -- from the origins of view rays_view (FrameParams::rays_o; 12 bytes per ray and round against ~512 per sample, L2-resident)
 // by the ray number its pix_idx stands for: o_in is ignored, and a ray handed to a helper wave needs no origin in its mail.
-template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false, bool RAYS = false,
+// RAYS is RAYS_NONE, RAYS_FULL or RAYS_DENSITY (nrf_device.h).  RAYS_DENSITY: the network phase evaluates sigma alone and cr, cg, cb
+// stay what they came in as (0; they travel in the tail-split mail as such); ws, dep, n_comp, the termination test and `alive` are
+// those of RAYS_FULL, from the same instructions on the same sigma.
+template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false, int RAYS = RAYS_NONE,
           uint32_t GP = GATHER_RUNTIME>
 __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams& P, const MarchConst& mc, const LdsMap& lm,
                                             const uint32_t* coarse_lds, const float* ctab_lds, int lane, const float (&o_in)[3],
@@ -869,7 +876,7 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
     // terminating sample is evaluated for nothing (the reference's own schedule wastes 8.6 % that way, an unconditional queue
     // of 8 here 2.4 %).  The per-round queue shrinks with T; per-ray semantics -- and so every pixel -- do not depend on it.
     float o[3] = {o_in[0], o_in[1], o_in[2]};
-    if constexpr (RAYS) {  // (a value of this round alone: nothing of it is carried from round to round)
+    if constexpr (RAYS != RAYS_NONE) {  // (a value of this round alone: nothing of it is carried from round to round)
       o[0] = o[1] = o[2] = 0.f;
       if (alive) {
         uint32_t pi = pix_idx;
@@ -942,7 +949,7 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
 
     if (S > 0) {
       // ---- network on the S queued samples (sample-major MFMA tiles)
-      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH)>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
+      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH), RAYS == RAYS_DENSITY>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
       wave_sync();
     }
     NRF_STAMP(t2);
@@ -960,9 +967,11 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
         const float wgt = alpha * T;
         ws += wgt;
         dep += wgt * dtc.y;  // depth += weight * t, t = composited t of this sample
-        cr += wgt * so.x;
-        cg += wgt * so.y;
-        cb += wgt * so.z;
+        if constexpr (RAYS != RAYS_DENSITY) {
+          cr += wgt * so.x;
+          cg += wgt * so.y;
+          cb += wgt * so.z;
+        }
         n_comp++;
         // `T < 1e-4` against a double literal: true exactly for T <= 9.99999974737875e-05f
         if (T <= 9.99999974737875e-05f) { terminated = true; break; }
@@ -1060,8 +1069,9 @@ __device__ __forceinline__ float4 finish_pixel(const FrameParams& P, const TileA
 // 128 VGPRs.  Small workgroups matter: a workgroup's LDS and wave slots are only released when its
 // slowest tile is done.
 // (the generic instance is bound by its LDS rows, not by registers: no 128-VGPR cap there)
-// RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray) -- instances of their own, nrf_kernels_rays.hip
-template <int NET, bool COARSE_LDS, int MARCH, bool PERTURB = false, bool RAYS = false>
+// RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray) -- instances of their own, nrf_kernels_rays.hip;
+// RAYS_DENSITY (NRF_RAYS_DENSITY_ONLY): their twins without direction encoding and colour network, nrf_kernels_rays_density.hip
+template <int NET, bool COARSE_LDS, int MARCH, bool PERTURB = false, int RAYS = RAYS_NONE>
 __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NET_WIDE ? 3 : 4)) void render_kernel(const DevModel M, const FrameParams P, const ViewBatch VB,
                                                      float4* __restrict__ rgba, float* __restrict__ depth,
                                                      unsigned long long* __restrict__ counters) {
@@ -1138,11 +1148,11 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   float o[3] = {V.org[0], V.org[1], V.org[2]};
   float d[3];
   bool has_ray = true;
-  if constexpr (RAYS) has_ray = load_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, in_img, o, d);
+  if constexpr (RAYS != RAYS_NONE) has_ray = load_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, in_img, o, d);
   else ray_dir(V.R, V.cam, px, py, d);
   float near, far;
   near_far(M.aabb, o, d, P.min_near, near, far);
-  if constexpr (RAYS) {
+  if constexpr (RAYS != RAYS_NONE) {
     if (!has_ray) near = far = 3.402823466e+38f;  // (what near_far gives a ray that misses the aabb)
     else clamp_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, near, far);
   }
@@ -1232,7 +1242,7 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
       }
 #endif
     }
-    if (alive) {  // direction encoding: only rays that will evaluate the network need it
+    if (RAYS != RAYS_DENSITY && alive) {  // direction encoding: only rays that will evaluate the colour network need it
       float u0 = 0.5f * d[0]; u0 = u0 + 0.5f;  // linear_transformer(0.5, 0.5), nerf_render.cu:313-314
       float u1 = 0.5f * d[1]; u1 = u1 + 0.5f;
       float u2 = 0.5f * d[2]; u2 = u2 + 0.5f;
@@ -1285,7 +1295,7 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   {
     const uint32_t rn = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
     float dn;
-    const float4 c = finish_pixel<RAYS>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
+    const float4 c = finish_pixel<RAYS != RAYS_NONE>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
     store_pixel(P, rgba, depth, k_local, lane, px, py, in_img, c, dn);
   }
   counters += (blockIdx.x % COUNTER_SLOTS) * 16;  // see COUNTER_SLOTS
@@ -1405,9 +1415,10 @@ static_assert(offsetof(PersistArgs, P) == (sizeof(DevModel) + alignof(FrameParam
 // FAST: nrf_options::fast_interp (opt-in single-rounding interpolation; register-resident instance only) -- instances of
 // their own, so that the shipped default symbols keep the bit-exact arithmetic (tests/test_abi_cpu.py checks their ISA)
 // RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray; every view's region of interest is its whole frame) --
-// instances of their own, nrf_kernels_rays.hip.  (FAST stays the last argument: tests/test_abi_cpu.py reads it off the symbol names)
+// instances of their own, nrf_kernels_rays.hip; RAYS_DENSITY: their density-only twins, nrf_kernels_rays_density.hip.
+// (FAST stays the last argument: tests/test_abi_cpu.py reads it off the symbol names)
 // GP: the gather plan (nrf_launch.h) -- GATHER_RUNTIME, or one of the static plans of the hot instance (nrf_kernels_hot_*.hip)
-template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, bool RAYS = false,
+template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, int RAYS = RAYS_NONE,
           uint32_t GP = GATHER_RUNTIME, bool FAST = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const DevModel M0, const FrameParams P0, const ViewBatch VB0,
                                                                               float4* __restrict__ rgba0, float* __restrict__ depth0,
@@ -1586,11 +1597,11 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     float o[3] = {V.org[0], V.org[1], V.org[2]};
     float d[3];
     bool has_ray = true;
-    if constexpr (RAYS) has_ray = load_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, in_img, o, d);
+    if constexpr (RAYS != RAYS_NONE) has_ray = load_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, in_img, o, d);
     else ray_dir(V.R, V.cam, px, py, d);
     float near, far;
     near_far(M.aabb, o, d, P.min_near, near, far);
-    if constexpr (RAYS) {
+    if constexpr (RAYS != RAYS_NONE) {
       if (!has_ray) near = far = 3.402823466e+38f;
       else clamp_ray(P, view, (uint32_t)py * (uint32_t)P.W + (uint32_t)px, near, far);
     }
@@ -1650,7 +1661,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     bool given = false;  // tail splitting: this lane's ray went to a helper wave, which stores its pixel
     const uint32_t pix_idx = P.tile_major ? (uint32_t)k_local * 64u + (uint32_t)lane : (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
     if (__ballot(alive) != 0ull) {
-      if (alive) encode_ray_dir<NET>(M, lm, lane, d);  // direction encoding of the rays that will evaluate the network
+      if (RAYS != RAYS_DENSITY && alive) encode_ray_dir<NET>(M, lm, lane, d);  // direction encoding of the rays that will evaluate the colour network
       wave_sync();
       NRF_STAMP(t_setup_done);
       const HelpArgs ha = {hl, lm.W - wave, view};
@@ -1669,7 +1680,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     // ---- get_image_and_depth (finish_pixel)
     float dn;
     const uint32_t rn = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
-    const float4 c = finish_pixel<RAYS>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
+    const float4 c = finish_pixel<RAYS != RAYS_NONE>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
 #ifdef NRF_PHASE_TIMING
     if (P.march_budget == 4095) {  // diagnostic: the depth plane carries the tile's cost (cycles / 1e6) and start time instead
       NRF_STAMP(t_tile_end);
@@ -1769,7 +1780,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const int sx = __builtin_signbitf(d[0]) ? 0 : 1;
     const int sy = __builtin_signbitf(d[1]) ? 0 : 1;
     const int sz = __builtin_signbitf(d[2]) ? 0 : 1;
-    if (mine) encode_ray_dir<NET>(M, lm, lane, d);
+    if (RAYS != RAYS_DENSITY && mine) encode_ray_dir<NET>(M, lm, lane, d);
     wave_sync();
     bool given = false;
     const HelpArgs ha = {hl, lm.W - wave, view};
@@ -1782,7 +1793,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const bool store = mine && !given;
     if (store) {  // get_image_and_depth, as in the tile loop
       float dn;  // (a helped ray is one of the caller's list: it was alive)
-      const float4 c = finish_pixel<RAYS>(P, acc, near, far, view, RAYS ? ray_number(P, pix_idx) : 0u, true, dn);
+      const float4 c = finish_pixel<RAYS != RAYS_NONE>(P, acc, near, far, view, RAYS != RAYS_NONE ? ray_number(P, pix_idx) : 0u, true, dn);
       store_ray_pixel<OUT8>(P, op.rgba, op.depth, pix_idx, c, dn);
     }
     if constexpr (U8) {  // (8-bit planes are row-major: the strip row of the rays' tile follows from a pixel index)
@@ -1866,6 +1877,7 @@ hipError_t launch_persistent_wide(const PersistLaunch& L);
 hipError_t launch_persistent_generic(const PersistLaunch& L);
 hipError_t launch_persistent_grid(const PersistLaunch& L);
 hipError_t launch_persistent_rays(const PersistLaunch& L);  // FrameParams::rays_o != nullptr, NET_HOT (nrf_kernels_rays.hip)
+hipError_t launch_persistent_rays_density(const PersistLaunch& L);  // its RAY_FLAG_DENSITY_ONLY twins, float planes (nrf_kernels_rays_density.hip)
 struct StripLaunch {
   const DevModel* M;
   const FrameParams* P;
@@ -1878,6 +1890,7 @@ struct StripLaunch {
 };
 hipError_t launch_strip(const StripLaunch& L);
 hipError_t launch_strip_rays(const StripLaunch& L);  // FrameParams::rays_o != nullptr (nrf_kernels_rays.hip)
+hipError_t launch_strip_rays_density(const StripLaunch& L);  // its RAY_FLAG_DENSITY_ONLY twins (nrf_kernels_rays_density.hip)
 void preload_hot();
 void preload_hot_qqfh();
 void preload_hot_qqhh();
@@ -1888,6 +1901,7 @@ void preload_generic();
 void preload_strip();
 void preload_grid();
 void preload_rays();
+void preload_rays_density();
 
 // one instance of the persistent form: WV waves per workgroup, WL = generic weights in LDS, 8-bit output / fast_interp chosen at run time
 // (GP: the gather plan, nrf_launch.h)

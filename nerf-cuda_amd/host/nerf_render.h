@@ -83,6 +83,7 @@ class NerfRender {
   // no limit / the renderer's background.  What a rasteriser passes to mix the NeRF into its scene: its G-buffer's hit distance
   // as t_max, its shaded colour as background.  The Image's depth is the normalised one: the metric depth plane
   // (NRF_RAYS_DEPTH_T) is a float plane an 8-bit Image cannot hold, and is reachable through the C call only.
+  // So is the density-only mode for shadow and occlusion rays (NRF_RAYS_DENSITY_ONLY): it renders float planes only.
   Image render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view, const void* t_min, const void* t_max,
                     const void* background);
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in

@@ -123,6 +123,7 @@ class HostFrame(C.Structure):
 
 NRF_HOST_RGB_ONLY = 1
 NRF_RAYS_DEPTH_T = 1  # nrf_rays.flags: the depth plane holds the accumulated sum of w * t, not its normalised form
+NRF_RAYS_DENSITY_ONLY = 4  # nrf_rays.flags: the density network alone -- alpha and depth as without it, rgb = (1 - alpha) * background
 
 
 class Rays(C.Structure):
@@ -664,7 +665,10 @@ class NerfHip:
         of t along the (not normalised) direction; a NaN entry, or a null pointer (0) for the whole array: no limit (an ENTRY of 0 is a
         limit like any other: t_max = 0 empties the ray) -- over a per-ray background, device fp32
         [n_views][rays_per_view][3] (0: the scalar bg_color).  flags: NRF_RAYS_DEPTH_T = the depth plane is the composited sum of
-        w * t (divide by alpha for the expected hit distance) instead of the normalised depth."""
+        w * t (divide by alpha for the expected hit distance) instead of the normalised depth; NRF_RAYS_DENSITY_ONLY (may be combined
+        with it; float outputs only) = shadow / occlusion rays: the density network alone is evaluated, alpha and depth are those of
+        the call without the flag bit for bit, and rgb = (1 - alpha) * background (the ray's entry, or bg_color) -- pass the light's
+        unshadowed radiance as background and its distance over |d| as t_max."""
         r = Rays(rays_o_ptr or None, rays_d_ptr or None, int(rays_per_view), t_min_ptr or None, t_max_ptr or None,
                  background_ptr or None, int(flags), 0)
         f = Frame()

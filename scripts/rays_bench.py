@@ -1,5 +1,5 @@
 """What rendering from caller-supplied rays costs against the pinhole path, on the flagship workload: the 1080p, T = 2^19
-base.json-shaped model in 16-view launches.  One process alternates five legs, so that all of them see the same box and clock:
+base.json-shaped model in 16-view launches.  One process alternates seven legs, so that all of them see the same box and clock:
 
   views          nrf_render_views of 16 orbit cameras (code nrf_render_rays does not touch: the baseline)
   rays           nrf_render_rays on the nrf_generate_rays output of the same cameras, persistent RAYS instance
@@ -7,11 +7,17 @@ base.json-shaped model in 16-view launches.  One process alternates five legs, s
   rays_clipped   nrf_render_rays_clipped on the same rays with t_max = +inf in every entry and a background array that repeats
                  bg_color: the limits limit nothing, so the leg prices the reads (4 + 12 B per ray) and renders the same frame
   rays_clipped_strip   the same through the per-strip RAYS instance
-(--lib: another build of the library, e.g. the parent commit's; a build without nrf_render_rays_clipped runs the first three legs.)
+  rays_density   nrf_render_rays_clipped on the same rays with NRF_RAYS_DENSITY_ONLY and no arrays: the density-only twin of the
+                 persistent RAYS instance (no direction encoding, no colour network) -- its full twin is the rays leg
+  rays_density_strip   the same through the per-strip instance -- its full twin is the rays_strip leg
+(--lib: another build of the library, e.g. the parent commit's; a build without nrf_render_rays_clipped runs the first three legs,
+one without the flag the first five.)
 
 Per leg: device ms per view (hipEvents around the call's launches, nrf_stats.render_ms) -- median, minimum, maximum over the
-repetitions --, samples, and the shader clock the persistent kernel measured in its launches (0: the per-strip kernel has no such
-stamp).  The frames of all legs are compared bit for bit first.  Prints one JSON object.
+repetitions --, samples, composited samples per view, and the shader clock the persistent kernel measured in its launches (0: the
+per-strip kernel has no such stamp).  The frames of all legs are compared bit for bit first; of a density-only leg the alpha and
+depth planes, and its rgb planes with (1 - alpha) * bg_color.  Medians and ratios leave out a leg's first repetition, which follows
+the read-back of that comparison.  Prints one JSON object.
 
 Run it under a time limit:   timeout -k 10 300 python3 scripts/rays_bench.py [--reps 7] [--out profiles/.../rays_bench.json]"""
 import argparse
@@ -84,6 +90,14 @@ if CLIPPED:
         LEGS[name] = lambda c=c: c.render_rays_clipped(rays_o.data_ptr(), rays_d.data_ptr(), W * H, 0, t_max.data_ptr(),
                                                         bg.data_ptr(), 0, n_views=V)
         CTX[name] = c
+    DENSITY = getattr(nh, "NRF_RAYS_DENSITY_ONLY", 4)
+    try:  # (a library from before the flag answers NRF_E_INVALID)
+        cp.render_rays_clipped(rays_o.data_ptr(), rays_d.data_ptr(), W * H, flags=DENSITY)
+        for name, c in (("rays_density", cp), ("rays_density_strip", cs)):
+            LEGS[name] = lambda c=c: c.render_rays_clipped(rays_o.data_ptr(), rays_d.data_ptr(), W * H, flags=DENSITY, n_views=V)
+            CTX[name] = c
+    except nh.NerfHipError as e:
+        assert e.code == nh.NRF_E_INVALID, e
 if args.legs:
     LEGS = {k: f for k, f in LEGS.items() if k == "views" or k in args.legs.split(",")}
     assert "rays" in LEGS, "the rays leg is the one the ratios are taken against"
@@ -95,12 +109,18 @@ for name, run in LEGS.items():
     frames[name] = [CTX[name].read_view_f32(v) for v in (0, V // 2, V - 1)]
 for name in list(LEGS)[1:]:
     for a, b in zip(frames[name], frames["views"]):
+        if "density" in name:  # alpha and depth of the full frame; rgb = the background that gets through, two roundings
+            alpha = a[0][..., 3]
+            through = ((np.float32(1) - alpha).astype(np.float32) * np.float32(nh.default_options().bg_color)).astype(np.float32)
+            assert np.array_equal(alpha.view(np.uint32), b[0][..., 3].view(np.uint32)) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), name
+            assert np.array_equal(a[0][..., :3], np.repeat(through[..., None], 3, axis=-1)), name
+            continue
         assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), name
 del frames
 
 ms = {k: [] for k in LEGS}
 clock = {k: [] for k in LEGS}
-samples = {}
+samples, composited = {}, {}
 for _ in range(args.reps):
     for name, run in LEGS.items():
         run()
@@ -108,25 +128,30 @@ for _ in range(args.reps):
         ms[name].append(st.render_ms / V)
         clock[name].append(st.shader_clock_mhz)
         samples[name] = int(st.n_samples)
+        composited[name] = int(st.n_composited)
 res = {"workload": f"{V} views of {W}x{H}, T = 2^19 base.json shape", "reps": args.reps, "lib": os.path.relpath(str(nh.LIB_PATH), ROOT), "legs": {}}
 for name in LEGS:
-    a = np.array(ms[name])
+    full = np.array(ms[name])
+    a = full[1:] if len(full) > 1 else full  # without the first repetition, which follows the read-back
+    ck = np.array(clock[name][1:] or clock[name])
     res["legs"][name] = {"ms_per_view_median": round(float(np.median(a)), 4), "ms_per_view_min": round(float(a.min()), 4),
                          "ms_per_view_max": round(float(a.max()), 4), "n_samples": samples[name],
-                         "shader_clock_mhz": round(float(np.median(clock[name])), 1),
-                         "ms_per_view_all": [round(float(x), 4) for x in a]}
+                         "n_composited_per_view": round(composited[name] / V, 1),
+                         "shader_clock_mhz": round(float(np.median(ck)), 1),
+                         "ms_per_view_all": [round(float(x), 4) for x in full]}
     print(f"{name:18s} {np.median(a):7.4f} ms/view (min {a.min():.4f}, max {a.max():.4f})  samples {samples[name]}  "
-          f"shader_clock_mhz {np.median(clock[name]):.0f}", file=sys.stderr, flush=True)
+          f"composited/view {composited[name] / V:.0f}  shader_clock_mhz {np.median(ck):.0f}", file=sys.stderr, flush=True)
 m = {k: res["legs"][k]["ms_per_view_median"] for k in LEGS}
 spread = (res["legs"]["views"]["ms_per_view_max"] - res["legs"]["views"]["ms_per_view_min"]) / m["views"]
 res["rays_over_views"] = round(m["rays"] / m["views"], 4)
-for a, b in (("rays_strip", "rays"), ("rays_clipped", "rays"), ("rays_clipped_strip", "rays_strip")):
+for a, b in (("rays_strip", "rays"), ("rays_clipped", "rays"), ("rays_clipped_strip", "rays_strip"), ("rays_density", "rays"),
+             ("rays_density_strip", "rays_strip")):
     if a in m and b in m:
         res[f"{a}_over_{b}"] = round(m[a] / m[b], 4)
 a = np.array(ms["rays"][1:] or ms["rays"])  # without the first repetition, which follows the read-back
 res["rays_run_to_run_spread"] = round(float((a.max() - a.min()) / np.median(a)), 4)
 res["views_run_to_run_spread"] = round(spread, 4)  # (max - min) / median of the baseline leg
-q1, q3 = np.percentile(np.array(ms["views"]), [25, 75])
+q1, q3 = np.percentile(np.array(ms["views"][1:] or ms["views"]), [25, 75])
 res["views_interquartile_spread"] = round(float((q3 - q1) / m["views"]), 4)
 print(json.dumps(res))
 if args.out:
