@@ -22,6 +22,7 @@
 #include "nrf_generic.h"
 #include "nrf_grid_plan.h"
 #include "nrf_launch.h"
+#include "nrf_model_plan.h"
 
 using namespace nrf;
 
@@ -42,431 +43,7 @@ int hip_fail(hipError_t e, const char* what) {
     if (_e != hipSuccess) return hip_fail(_e, #expr); \
   } while (0)
 
-inline uint32_t next_multiple(uint32_t v, uint32_t d) { return (v + d - 1) / d * d; }
-
-// T/include/tiny-cuda-nn/encodings/grid.h:899-931 (ctor) and :186-190 (kernel): the level geometry is
-// computed once, on the host, with libm's exp2f/log2f, and handed to every kernel as constants.
-int compute_level_table(const nrf_model_desc& d, nrf_level_table& t) {
-  if (d.n_levels == 0 || d.n_levels > 16) return fail(NRF_E_UNSUPPORTED, "n_levels must be 1..16");
-  if (d.log2_hashmap_size > 31) return fail(NRF_E_INVALID, "log2_hashmap_size must be <= 31");
-  std::memset(&t, 0, sizeof(t));
-  t.n_levels = d.n_levels;
-  const float log2_pls = std::log2(d.per_level_scale);
-  uint32_t offset = 0;
-  for (uint32_t i = 0; i < d.n_levels; ++i) {
-    const float scale = exp2f((float)i * log2_pls) * (float)d.base_resolution - 1.0f;
-    const uint32_t res = (uint32_t)ceilf(scale) + 1;
-    const uint32_t max_params = std::numeric_limits<uint32_t>::max() / 2;
-    uint32_t params = powf((float)res, 3.0f) > (float)max_params ? max_params : res * res * res;
-    params = next_multiple(params, 8u);
-    if (d.grid_type == NRF_GRID_TILED) {
-      const uint32_t b3 = d.base_resolution * d.base_resolution * d.base_resolution;
-      params = params < b3 ? params : b3;
-    } else if (d.grid_type == NRF_GRID_HASH) {
-      const uint32_t T = 1u << d.log2_hashmap_size;
-      params = params < T ? params : T;
-    } else if (d.grid_type != NRF_GRID_DENSE) {
-      return fail(NRF_E_INVALID, "GridEncoding: invalid grid type");
-    }
-    t.offset[i] = offset;
-    t.resolution[i] = res;
-    t.scale[i] = scale;
-    offset += params;
-  }
-  t.offset[d.n_levels] = offset;
-  return NRF_OK;
-}
-
-uint32_t dir_raw_width(const nrf_model_desc& d) {
-  switch (d.dir_encoding) {
-    case NRF_DIR_SH: return d.sh_degree * d.sh_degree;
-    case NRF_DIR_FREQUENCY: return 6 * d.n_frequencies;
-    case NRF_DIR_IDENTITY: return 3;
-    default: return 0;
-  }
-}
-
-// n_params of NerfNetwork (nerf_network.h:273-291): density MLP | rgb MLP | grid | dir enc (0)
-int expected_params(const nrf_model_desc& d, const nrf_level_table& t, uint64_t& n) {
-  const uint32_t raw = dir_raw_width(d);
-  if (raw == 0) return fail(NRF_E_UNSUPPORTED, "unknown dir encoding");
-  const uint64_t Wn = d.n_neurons;
-  const uint64_t feat = next_multiple(d.n_levels * d.n_features_per_level, 16u);
-  const uint64_t rgb_in = next_multiple(next_multiple(raw, 16u) + 16u, 16u);
-  if (d.density_hidden_layers < 1 || d.rgb_hidden_layers < 1)
-    return fail(NRF_E_INVALID, "FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");  // fully_fused_mlp.cu:653-655
-  auto mlp = [&](uint64_t in, uint64_t hidden) { return in * Wn + (hidden - 1) * Wn * Wn + Wn * 16; };
-  n = mlp(feat, d.density_hidden_layers) + mlp(rgb_in, d.rgb_hidden_layers) +
-      (uint64_t)t.offset[d.n_levels] * d.n_features_per_level;
-  return NRF_OK;
-}
-
-// fp16 weight fragments for v_mfma_f32_16x16x32_f16 (see nrf_device.h mlp_tiles):
-// fragment f, lane l, element j  =  W[16m + (l&15)][kmap(s, l>>4, j)]
-//   input layers   kmap(g,j) = 2(4(j>>1) + g) + (j&1)      (density: lane group g holds levels g, 4+g, 8+g, 12+g)
-//                  kmap(g,j) = j<4 ? 4g+j : 16+4g+(j-4)    (rgb: [density out | dir enc])
-//   hidden->next   kmap(s,g,j) = 16(2s + (j>>2)) + 4g + (j&3)   (a D fragment re-used in-lane as B)
-void pack_fragments(const std::vector<_Float16>& w16, uint32_t rgb_in, std::vector<_Float16>& frags) {
-  frags.assign((size_t)N_FRAGS_WIDE_ALL * 64 * 8, (_Float16)0.0f);
-  const _Float16* D0 = w16.data();              // [64][32]
-  const _Float16* D1 = D0 + 64 * 32;            // [16][64]
-  const _Float16* R0 = D1 + 16 * 64;            // [64][rgb_in]: 32 for a 16-wide direction encoding, up to 96 (wide instance)
-  const _Float16* R1 = R0 + 64 * (size_t)rgb_in;  // [64][64]
-  const _Float16* R2 = R1 + 64 * 64;            // [16][64]
-  auto khid = [](int s, int g, int j) { return 16 * (2 * s + (j >> 2)) + 4 * g + (j & 3); };
-  auto put = [&](int f, const _Float16* Wm, int in, int m, auto kmap) {
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int k = kmap(l >> 4, j);
-        frags[((size_t)f * 64 + l) * 8 + j] = k < in ? Wm[(size_t)(16 * m + (l & 15)) * in + k] : (_Float16)0.0f;
-      }
-  };
-  for (int m = 0; m < 4; ++m) put(FRAG_D0 + m, D0, 32, m, [](int g, int j) { return 2 * (4 * (j >> 1) + g) + (j & 1); });
-  for (int m = 0; m < 4; ++m) put(FRAG_D0_NATURAL + m, D0, 32, m, [](int g, int j) { return 8 * g + j; });
-  for (int s = 0; s < 2; ++s) put(FRAG_D1 + s, D1, 64, 0, [&](int g, int j) { return khid(s, g, j); });
-  for (int m = 0; m < 4; ++m) put(FRAG_R0 + m, R0, (int)rgb_in, m, [](int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); });
-  for (int s = 1; s < RK_WIDE; ++s)  // wide instance: the columns beyond the first 32, natural order; zero beyond rgb_in
-    for (int m = 0; m < 4; ++m) put(FRAG_R0X + 4 * (s - 1) + m, R0, (int)rgb_in, m, [&](int g, int j) { return 32 * s + 8 * g + j; });
-  for (int m = 0; m < 4; ++m)
-    for (int s = 0; s < 2; ++s) put(FRAG_R1 + 2 * m + s, R1, 64, m, [&](int g, int j) { return khid(s, g, j); });
-  for (int s = 0; s < 2; ++s) put(FRAG_R2 + s, R2, 64, 0, [&](int g, int j) { return khid(s, g, j); });
-}
-
-// GRID instances (nrf_render.h grid_features): base.json's MLPs behind a grid of F features per level, feat_w = its padded width
-// (16 or 32).  The hot layout (fragments 0 .. N_FRAGS - 1) with the first density layer's K order of that grid: lane group g
-// holds, in this order, the features of the levels {g, 4 + g, ...} it encodes --
-//   F = 2: kmap(g, j) = 2 (4 (j >> 1) + g) + (j & 1)     F = 4: 4 (4 (j >> 2) + g) + (j & 3)     F = 8: 8 g + j     F = 1: 4 j + g (j < 4)
-// -- and zero columns where the grid has no level (k >= feat_w, or a padded feature of feat_w itself).
-void pack_fragments_grid(const std::vector<_Float16>& w16, uint32_t feat_w, uint32_t rgb_in, uint32_t F, std::vector<_Float16>& frags) {
-  frags.assign((size_t)N_FRAGS * 64 * 8, (_Float16)0.0f);
-  const _Float16* D0 = w16.data();                  // [64][feat_w]
-  const _Float16* D1 = D0 + 64 * (size_t)feat_w;    // [16][64]
-  const _Float16* R0 = D1 + 16 * 64;                // [64][rgb_in]
-  const _Float16* R1 = R0 + 64 * (size_t)rgb_in;    // [64][64]
-  const _Float16* R2 = R1 + 64 * 64;                // [16][64]
-  auto khid = [](int s, int g, int j) { return 16 * (2 * s + (j >> 2)) + 4 * g + (j & 3); };
-  auto put = [&](int f, const _Float16* Wm, int in, int m, auto kmap) {
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int k = kmap(l >> 4, j);
-        frags[((size_t)f * 64 + l) * 8 + j] = k < in ? Wm[(size_t)(16 * m + (l & 15)) * in + k] : (_Float16)0.0f;
-      }
-  };
-  const int Fi = (int)F;
-  for (int m = 0; m < 4; ++m)
-    put(FRAG_D0 + m, D0, (int)feat_w, m, [Fi](int g, int j) {
-      if (Fi == 1) return j < 4 ? 4 * j + g : (1 << 20);  // one feature per level: level 4 j + g; the lane's upper four are zero columns
-      return Fi == 2 ? 2 * (4 * (j >> 1) + g) + (j & 1) : (Fi == 4 ? 4 * (4 * (j >> 2) + g) + (j & 3) : 8 * g + j);
-    });
-  for (int s = 0; s < 2; ++s) put(FRAG_D1 + s, D1, 64, 0, [&](int g, int j) { return khid(s, g, j); });
-  for (int m = 0; m < 4; ++m) put(FRAG_R0 + m, R0, (int)rgb_in, m, [](int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); });
-  for (int m = 0; m < 4; ++m)
-    for (int s = 0; s < 2; ++s) put(FRAG_R1 + 2 * m + s, R1, 64, m, [&](int g, int j) { return khid(s, g, j); });
-  for (int s = 0; s < 2; ++s) put(FRAG_R2 + s, R2, 64, 0, [&](int g, int j) { return khid(s, g, j); });
-}
-
-// The same fragment order for 16 / 32 / 128 neurons (nrf_device.h MlpShape<W>): D0 [W][32] | D1 [16][W] | R0 [W][32] | R1 [W][W] | R2 [16][W],
-// MT = W / 16 row tiles, KS = ceil(W / 32) K steps; columns beyond a matrix's width are zero (W = 16: the upper half of the one step).
-void pack_fragments_width(const std::vector<_Float16>& w16, int Wd, std::vector<_Float16>& frags) {
-  const int MT = Wd / 16, KS = (Wd + 31) / 32;
-  const int fD1 = MT, fR0 = MT + KS, fR1 = 2 * MT + KS, fR2 = 2 * MT + KS + MT * KS, n = 2 * MT + 2 * KS + MT * KS;
-  frags.assign((size_t)n * 64 * 8, (_Float16)0.0f);
-  const _Float16* D0 = w16.data();                 // [W][32]
-  const _Float16* D1 = D0 + (size_t)Wd * 32;       // [16][W]
-  const _Float16* R0 = D1 + (size_t)16 * Wd;       // [W][32]
-  const _Float16* R1 = R0 + (size_t)Wd * 32;       // [W][W]
-  const _Float16* R2 = R1 + (size_t)Wd * Wd;       // [16][W]
-  auto khid = [](int s, int g, int j) { return 16 * (2 * s + (j >> 2)) + 4 * g + (j & 3); };
-  auto put = [&](int f, const _Float16* Wm, int in, int m, auto kmap) {
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int k = kmap(l >> 4, j);
-        frags[((size_t)f * 64 + l) * 8 + j] = k < in ? Wm[(size_t)(16 * m + (l & 15)) * in + k] : (_Float16)0.0f;
-      }
-  };
-  for (int m = 0; m < MT; ++m) put(m, D0, 32, m, [](int g, int j) { return 2 * (4 * (j >> 1) + g) + (j & 1); });
-  for (int s = 0; s < KS; ++s) put(fD1 + s, D1, Wd, 0, [&](int g, int j) { return khid(s, g, j); });
-  for (int m = 0; m < MT; ++m) put(fR0 + m, R0, 32, m, [](int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); });
-  for (int m = 0; m < MT; ++m)
-    for (int s = 0; s < KS; ++s) put(fR1 + KS * m + s, R1, Wd, m, [&](int g, int j) { return khid(s, g, j); });
-  for (int s = 0; s < KS; ++s) put(fR2 + s, R2, Wd, 0, [&](int g, int j) { return khid(s, g, j); });
-}
-
-// DEPTH instance (nrf_device.h DF_*, mlp_tiles_depth): 64 neurons, nd / nr hidden layers in the density / rgb MLP.  Parameter order
-// (tcnn): D0 [64][32] | (nd - 1) x [64][64] | D1 [16][64] | R0 [64][32] | (nr - 1) x [64][64] | R2 [16][64].  DEPTH_FRAGS fragments,
-// unused ones zero.
-void pack_fragments_depth(const std::vector<_Float16>& w16, int nd, int nr, std::vector<_Float16>& frags) {
-  frags.assign((size_t)DEPTH_FRAGS * 64 * 8, (_Float16)0.0f);
-  const int xd = nd - 1, xr = nr - 1;
-  const _Float16* D0 = w16.data();
-  const _Float16* DW = D0 + 64 * 32;
-  const _Float16* D1 = DW + (size_t)xd * 64 * 64;
-  const _Float16* R0 = D1 + 16 * 64;
-  const _Float16* RW = R0 + 64 * 32;
-  const _Float16* R2 = RW + (size_t)xr * 64 * 64;
-  auto khid = [](int s, int g, int j) { return 16 * (2 * s + (j >> 2)) + 4 * g + (j & 3); };
-  auto put = [&](int f, const _Float16* Wm, int in, int m, auto kmap) {
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int k = kmap(l >> 4, j);
-        frags[((size_t)f * 64 + l) * 8 + j] = k < in ? Wm[(size_t)(16 * m + (l & 15)) * in + k] : (_Float16)0.0f;
-      }
-  };
-  for (int m = 0; m < 4; ++m) put(DF_D0 + m, D0, 32, m, [](int g, int j) { return 2 * (4 * (j >> 1) + g) + (j & 1); });
-  for (int s = 0; s < 2; ++s) put(DF_D1 + s, D1, 64, 0, [&](int g, int j) { return khid(s, g, j); });
-  for (int m = 0; m < 4; ++m) put(DF_R0 + m, R0, 32, m, [](int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); });
-  for (int s = 0; s < 2; ++s) put(DF_R2 + s, R2, 64, 0, [&](int g, int j) { return khid(s, g, j); });
-  for (int e = 0; e < xd + xr; ++e) {
-    const _Float16* Wm = e < xd ? DW + (size_t)e * 64 * 64 : RW + (size_t)(e - xd) * 64 * 64;
-    for (int m = 0; m < 4; ++m)
-      for (int s = 0; s < 2; ++s) put(DF_WW + 8 * e + 2 * m + s, Wm, 64, m, [&](int g, int j) { return khid(s, g, j); });
-  }
-}
-
-// Generic instance (nrf_generic.h gen_layer): fragment (m, s) of a layer W[N][K], lane l, element j =
-// W[16 m + (l & 15)][32 s + 8 (l >> 4) + j]  (natural K order), zero beyond K.
-void pack_generic_layer(const _Float16* Wm, uint32_t N, uint32_t K, std::vector<_Float16>& frags) {
-  const uint32_t n_tiles = N / 16, k_steps = (K + 31) / 32;
-  for (uint32_t m = 0; m < n_tiles; ++m)
-    for (uint32_t s = 0; s < k_steps; ++s)
-      for (uint32_t l = 0; l < 64; ++l)
-        for (uint32_t j = 0; j < 8; ++j) {
-          const uint32_t k = 32 * s + 8 * (l >> 4) + j;
-          frags.push_back(k < K ? Wm[(size_t)(16 * m + (l & 15)) * K + k] : (_Float16)0.0f);
-        }
-}
-
-// bytes of the generic instance's weight fragments: pack_generic_layer's 1 KiB per 16 x 32 tile of every layer of the two MLPs
-uint32_t generic_frag_bytes(const nrf_model_desc& d, const GenModel& G) {
-  const uint32_t Wn = d.n_neurons;
-  auto tiles = [](uint32_t N, uint32_t K) { return (N / 16) * ((K + 31) / 32); };
-  auto mlp = [&](uint32_t in, uint32_t hidden) { return tiles(Wn, in) + (hidden - 1) * tiles(Wn, Wn) + tiles(16u, Wn); };
-  return 1024u * (mlp(G.feat_w, d.density_hidden_layers) + mlp(G.rgb_in, d.rgb_hidden_layers));
-}
-
 // R/include/nerf-cuda/render_utils.h:68-77
-// The descriptor checks of nrf_load_model that come before the old model is released: what the reference's vocabulary allows
-// (T/.../grid.h:1403-1411, T/src/fully_fused_mlp.cu:700-725, 653-655; spherical_harmonics.h:394-412); anything outside is
-// refused loudly, never emulated on the CPU
-int validate_model(const nrf_model_desc& d, nrf_level_table& lv) {
-  if (d.abi_version != NRF_ABI_VERSION) return fail(NRF_E_INVALID, "abi_version mismatch");
-  const uint32_t F = d.n_features_per_level;
-  if (F != 1 && F != 2 && F != 4 && F != 8) return fail(NRF_E_INVALID, "GridEncoding: n_features_per_level must be 1, 2, 4, or 8.");
-  if (d.interpolation > NRF_INTERP_SMOOTHSTEP) return fail(NRF_E_INVALID, "Invalid interpolation type");
-  if (d.n_neurons != 16 && d.n_neurons != 32 && d.n_neurons != 64 && d.n_neurons != 128)
-    return fail(NRF_E_INVALID, "FullyFusedMLP: n_neurons must be 16, 32, 64 or 128");
-  if (d.density_hidden_layers < 1 || d.rgb_hidden_layers < 1)
-    return fail(NRF_E_INVALID, "FullyFusedMLP requires at least 1 hidden layer (3 layers in total).");
-  if (d.density_hidden_layers + d.rgb_hidden_layers + 2 > (uint32_t)GEN_MAX_LAYERS)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: more than 24 layers in the two MLPs together");
-  if (d.density_n_output < 1 || d.density_n_output > 16)  // wider outputs take tcnn's CUTLASS last layer (out of scope)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: density n_output_dims must be 1..16");
-  const uint32_t raw = dir_raw_width(d);
-  if (d.dir_encoding == NRF_DIR_SH && (d.sh_degree < 1 || d.sh_degree > 8))
-    return fail(NRF_E_INVALID, "SphericalHarmonics: degree must be 1..8");
-  if (raw == 0 || next_multiple(raw, 16u) > (uint32_t)GEN_MAX_DIR_W)
-    return fail(NRF_E_UNSUPPORTED, "HIP path: direction encoding must have 1..112 outputs (after padding to 16)");
-  if (d.density_grid_size < 2 || d.density_grid_size >= (1u << 24) || d.cascade < 1)
-    return fail(NRF_E_INVALID, "bad density grid geometry");
-  if (!(d.bound > 0.0f)) return fail(NRF_E_INVALID, "bound must be positive");
-  int rc = compute_level_table(d, lv);
-  if (rc) return rc;
-  uint64_t expect = 0;
-  rc = expected_params(d, lv, expect);
-  if (rc) return rc;
-  if (d.n_params != expect)  // R/include/nerf-cuda/nerf_network.h:425-427
-    return fail(NRF_E_PARAMS, "Can't set params because number of parameters and model size do not match with each other.");
-  const uint64_t Hh = d.density_grid_size;
-  const uint64_t cells = Hh * Hh * Hh * d.cascade;
-  if (d.density_grid && d.n_density_grid != cells)  // R/src/nerf_render.cu:467-469
-    return fail(NRF_E_PARAMS, "Incompatible number of grid cascades.");
-  if (cells >= (1ull << 32)) return fail(NRF_E_UNSUPPORTED, "density grid too large");
-  return NRF_OK;
-}
-
-// What a model descriptor makes of the device side, decided without a device (nrf_debug_plan: tests/test_instance_plan_cpu.py).
-struct ModelPlan {
-  int rc;                    // NRF_OK, or the refusal (fail() has set the message)
-  nrf_level_table lv;
-  LevelParams lp[16];        // the device's level table: index modes, entry offsets, byte constants, quad copies
-  GenModel gen;              // the generic description without its layers (valid unless stage == NET_HOT)
-  uint32_t gen_wave_bytes;   // LDS bytes per wave of its direction + activation rows (0 when stage == NET_HOT)
-  bool generic_grid;         // a level of LV_GENERIC index arithmetic
-  int own;                   // NET_*: the instance that renders the frames when its march tables fit (plan_grid)
-  int stage;                 // NET_HOT, NET_WIDE or NET_GENERIC: the stage entry points, the per-strip kernel, the fallback
-  uint32_t quad_mask, quad_far;  // DevModel::quad_mask / quad_far
-  uint32_t uni_modes;        // DevModel::uni_modes
-  uint32_t gather_plan;      // DevModel::gather_plan: the static gather plan of the hot instance the steps' forms match, or GATHER_RUNTIME
-  uint64_t table_ref_bytes;  // device bytes of the reference-order table
-  uint64_t table_bytes;      // ... and of the quad copies behind it
-};
-
-// 2 bits per unrolled step jl of the fused kernel (DevModel::uni_modes): its existing levels are all dense (1) / all power-of-two hashed (2)
-uint32_t uni_modes_of(const LevelParams* lp, uint32_t L) {
-  uint32_t uni = 0;
-  for (int jl = 0; jl < 4; ++jl) {
-    bool all_dense = true, all_hash = true;
-    for (int g = 0; g < 4; ++g) {
-      if ((uint32_t)(4 * jl + g) >= L) continue;  // (a level the grid does not have: its lanes are masked, grid_features)
-      all_dense = all_dense && lp[4 * jl + g].mode == LV_DENSE;
-      all_hash = all_hash && lp[4 * jl + g].mode == LV_HASH_POW2;
-    }
-    uni |= (all_dense ? 1u : (all_hash ? 2u : 0u)) << (2 * jl);
-  }
-  return uni;
-}
-
-// budget_mb: bytes of quad copies allowed (MiB); max_quad_steps: unrolled steps (four levels each) that may have them;
-// static_gather: the hot instance may run under a static gather plan (NRF_GATHER_PLAN=0: never)
-ModelPlan plan_model(const nrf_model_desc& d, bool allow_own, uint64_t budget_mb, int max_quad_steps, bool static_gather = true) {
-  ModelPlan p;
-  std::memset(&p, 0, sizeof(p));
-  p.rc = validate_model(d, p.lv);
-  if (p.rc) return p;
-  const nrf_level_table& lv = p.lv;
-  const uint32_t F = d.n_features_per_level, L = d.n_levels, Wn = d.n_neurons;
-  for (uint32_t l = 0; l < L; ++l) {
-    LevelParams& Lv = p.lp[l];
-    Lv.scale = lv.scale[l];
-    Lv.res = lv.resolution[l];
-    Lv.size = lv.offset[l + 1] - lv.offset[l];
-    Lv.hashed = d.grid_type == NRF_GRID_HASH;
-    // replay grid_index's stride loop (grid.h:106-114) in uint32 to classify the level
-    uint32_t stride = 1, mult[3] = {0, 0, 0};  // mult: what grid_index multiplies x, y, z with (0: the term is skipped)
-    int dims = 0;
-    for (; dims < 3 && stride <= Lv.size; ++dims) {
-      mult[dims] = stride;
-      stride *= Lv.res;  // uint32, as in the reference: wraps for res^3 >= 2^32
-    }
-    const bool uses_hash = Lv.hashed && Lv.size < stride;
-    const bool pow2_size = Lv.size >= 2 && (Lv.size & (Lv.size - 1)) == 0;
-    if (uses_hash && pow2_size) Lv.mode = LV_HASH_POW2;
-    else if (!uses_hash && dims == 3 && Lv.res >= 2 && (uint64_t)Lv.res * Lv.res * Lv.res <= Lv.size) Lv.mode = LV_DENSE;
-    else if (!uses_hash && pow2_size && dims >= 1) Lv.mode = LV_ADD_POW2;  // (x + y * mult[1] + z * mult[2]) & (size - 1), see nrf_device.h
-    else Lv.mode = LV_GENERIC;
-    Lv.my_b = mult[1] << 2;  // (the hashed levels' constants replace these below)
-    Lv.mz_b = mult[2] << 2;
-    p.generic_grid = p.generic_grid || Lv.mode == LV_GENERIC;
-  }
-  // The instance: base.json's shape (F = 2 x 16 levels, Linear; 64 neurons, 1 + 2 hidden layers; a 16-wide direction encoding;
-  // ReLU hidden, density output None, rgb output None or Sigmoid, sigma Exponential) is NET_HOT.  Each register-resident
-  // instance relaxes one axis of it; everything else is the generic instance.
-  GenModel& G = p.gen;
-  G.F = F; G.interp = d.interpolation; G.n_levels = L; G.feat_raw = L * F; G.feat_w = next_multiple(G.feat_raw, 16u);
-  G.feat_k = next_multiple(G.feat_w, 32u); G.width = Wn; G.dir_raw = dir_raw_width(d); G.dir_w = next_multiple(G.dir_raw, 16u);
-  G.rgb_in = 16u + G.dir_w;
-  G.n_dens = d.density_hidden_layers + 1; G.n_rgb = d.rgb_hidden_layers + 1;
-  G.act_stride = std::max(G.feat_k, next_multiple(Wn, 32u)) + 8;  // +16 bytes: consecutive rows start 4 banks apart (ds_read_b128 of 16 rows: conflict-free)
-  G.dir_stride = G.dir_w + 8;
-  const uint32_t dir_w = G.dir_w;
-  const bool grid_base = !p.generic_grid && F == 2 && L == 16 && d.interpolation == NRF_INTERP_LINEAR;
-  const bool mlp_base = Wn == 64 && d.density_hidden_layers == 1 && d.rgb_hidden_layers == 2;
-  const bool dir16 = dir_w == 16;
-  const bool relu = d.density_activation == NRF_ACT_RELU && d.rgb_activation == NRF_ACT_RELU;
-  auto native = [](uint32_t a) {  // (nrf_device.h activate_native; Sine keeps the generic instance)
-    return a == NRF_ACT_RELU || a == NRF_ACT_NONE || a == NRF_ACT_EXPONENTIAL || a == NRF_ACT_SIGMOID || a == NRF_ACT_SQUAREPLUS || a == NRF_ACT_SOFTPLUS;
-  };
-  const bool acts_native = native(d.density_activation) && native(d.rgb_activation);
-  const bool outputs_base = d.density_output_activation == NRF_ACT_NONE && d.sigma_activation == NRF_ACT_EXPONENTIAL &&
-                            (d.rgb_output_activation == NRF_ACT_NONE || d.rgb_output_activation == NRF_ACT_SIGMOID);
-  // a Frequency encoding of 32..80 values: NET_WIDE (the first rgb layer in RK_WIDE K steps); SH of degree 5..8: NET_WIDE_SH
-  const bool freq_wide = dir_w > 16 && dir_w <= 16u * (2u * RK_WIDE - 1u) && d.dir_encoding == NRF_DIR_FREQUENCY;
-  const bool sh_wide = dir_w > 16 && dir_w <= 64 && d.dir_encoding == NRF_DIR_SH;
-  const uint32_t extra_layers = (d.density_hidden_layers - 1) + (d.rgb_hidden_layers - 1);
-  int own = NET_GENERIC;
-  if (!outputs_base) own = NET_GENERIC;
-  else if (grid_base && mlp_base && relu && dir16) own = NET_HOT;
-  else if (grid_base && mlp_base && relu && freq_wide) own = NET_WIDE;
-  else if (!allow_own) own = NET_GENERIC;  // (NRF_WIDTH_INSTANCES=0: A/B runs)
-  else if (grid_base && mlp_base && relu && sh_wide) own = NET_WIDE_SH;
-  else if (grid_base && dir16 && relu && Wn != 64 && d.density_hidden_layers == 1 && d.rgb_hidden_layers == 2)
-    own = Wn == 16 ? NET_W16 : (Wn == 32 ? NET_W32 : NET_W128);  // tcnn's other FullyFusedMLP widths
-  else if (grid_base && dir16 && Wn == 64 && acts_native && extra_layers <= (uint32_t)DEPTH_MAX_WW)
-    own = relu ? NET_DEPTH : NET_ACT;  // other numbers of hidden layers (runtime), hidden activations other than ReLU
-  else if (!p.generic_grid && !grid_base && L * F <= 32 && mlp_base && dir16 && relu)
-    own = F == 1 ? NET_GRID1 : (F == 2 ? NET_GRID2 : (F == 4 ? NET_GRID4 : NET_GRID8));  // another grid in front of base.json's MLPs
-  p.own = own;
-  p.stage = own == NET_HOT || own == NET_WIDE ? own : NET_GENERIC;
-  p.gen_wave_bytes = p.stage != NET_HOT ? gen_dir_bytes(G) + gen_act_bytes(G) : 0u;
-  if (p.stage == NET_GENERIC && render_strip_lds_fixed_bytes(NET_GENERIC, p.gen_wave_bytes) > (int)CU_LDS_BYTES) {
-    p.rc = fail(NRF_E_UNSUPPORTED, "HIP path: this network shape needs more LDS than a CU has");
-    return p;
-  }
-  // Device copy of the table: the reference's entries level by level; a dense level is followed by
-  // res^2 + res + 1 copies of its first entries so that x + y*res + z*res^2 (at most
-  // size + res^2 + res when a +1 corner sits on the x = 1 / y = 1 / z = 1 face) needs no modulo.
-  uint64_t entries = 0;
-  for (uint32_t l = 0; l < L; ++l) {
-    LevelParams& Lv = p.lp[l];
-    if (Lv.mode == LV_HASH_POW2 || Lv.mode == LV_ADD_POW2)  // aligned to its own (power-of-two) size: `index & mask | offset` (level_gather)
-      entries = (entries + Lv.size - 1) / Lv.size * Lv.size;
-    Lv.offset = (uint32_t)entries;
-    entries += Lv.size;
-    if (Lv.mode == LV_DENSE) entries += (uint64_t)Lv.res * Lv.res + Lv.res + 1;
-  }
-  p.table_ref_bytes = entries * F * 2;
-  if (p.table_ref_bytes >= (1ull << 32)) {  // level_gather addresses the table by 32-bit byte offsets
-    p.rc = fail(NRF_E_UNSUPPORTED, "hash tables of 4 GiB or more are not supported");
-    return p;
-  }
-  // Cell-major quad copies (round 6; nrf_device.h level_gather_quad) behind the reference-order table, for the instances whose
-  // network phase is network_from_lds with an F = 2 x 16 grid (the hot instance, its wide / width / depth forms): per cell
-  // (x, y, z), x, y < res, z <= res, the four entries of the corners (x | x + 1, y | y + 1, z) as grid_index (grid.h:100-117)
-  // names them.  The reference-order table stays: every other kernel (stage entry points, generic instance) reads it.
-  // A step of the fused kernel (levels 4 jl .. 4 jl + 3, one per lane group) takes quads as a whole or not at all (steps that
-  // mix the two forms run both instruction streams: measured no faster, profiles/r06/quad_sweep.txt); steps are granted in order
-  // while their copies fit the budget (nrf_model_desc.gather_copy_budget_mb).  Copies that end beyond the 4 GiB a buffer
-  // resource's byte offset reaches are FAR: addressed in 16-byte units from the table base (level_gather_quad_far).
-  p.table_bytes = p.table_ref_bytes;
-  if (own != NET_GENERIC && net_grid_f(own) == 0) {
-    uint64_t budget = budget_mb << 20;
-    uint64_t end_bytes = (p.table_ref_bytes + 15) & ~15ull;
-    for (int jl = 0; jl < max_quad_steps; ++jl) {
-      uint64_t step_bytes = 0;
-      bool ok = true;
-      for (int g = 0; g < 4; ++g) {
-        const LevelParams& Lv = p.lp[4 * jl + g];
-        ok = ok && (Lv.mode == LV_DENSE || Lv.mode == LV_HASH_POW2) && Lv.res >= 2 && Lv.res < 1024u;  // (res^2 << 4 < 2^24)
-        step_bytes += (uint64_t)Lv.res * Lv.res * ((uint64_t)Lv.res + 1) * 16;
-      }
-      if (!ok || step_bytes > budget || end_bytes + step_bytes >= (1ull << 36)) continue;
-      const bool far = end_bytes + step_bytes >= (1ull << 32);
-      if (far && own == NET_WIDE) continue;  // (NET_WIDE is compiled without the far form: nrf_render.h network_from_lds)
-      budget -= step_bytes;
-      p.quad_mask |= 15u << (4 * jl);
-      if (far) p.quad_far |= 1u << jl;
-      for (int g = 0; g < 4; ++g) {
-        LevelParams& Lv = p.lp[4 * jl + g];
-        const uint32_t res = Lv.res;
-        Lv.q_off_b = far ? (uint32_t)(end_bytes >> 4) : (uint32_t)end_bytes;
-        Lv.q_my_b = far ? res : res << 4;
-        Lv.q_mz_b = far ? res * res : (res * res) << 4;
-        Lv.q_max = res - 1;
-        end_bytes += (uint64_t)res * res * (res + 1) * 16;
-      }
-    }
-    p.table_bytes = end_bytes;
-  }
-  // byte-offset constants of level_gather / level_gather_wide / level_gather_f1: an entry is 2 F bytes (the generic instance's
-  // literal index arithmetic, gen_level, does not read them)
-  const uint32_t sh_b = F == 8 ? 4u : (F == 4 ? 3u : (F == 1 ? 1u : 2u));
-  for (LevelParams& Lv : p.lp) {
-    const bool hashed_pow2 = Lv.mode == LV_HASH_POW2;
-    Lv.off_b = Lv.offset << sh_b;
-    if (hashed_pow2) {
-      Lv.my_b = 2654435761u << sh_b;
-      Lv.mz_b = 805459861u << sh_b;
-    } else {  // the additive multipliers of the stride loop above (dense: res, res^2; LV_ADD_POW2: possibly wrapped / 0)
-      Lv.my_b = (Lv.my_b >> 2) << sh_b;
-      Lv.mz_b = (Lv.mz_b >> 2) << sh_b;
-    }
-    Lv.mask_b = (hashed_pow2 || Lv.mode == LV_ADD_POW2) ? ((Lv.size - 1) << sh_b) : 0xffffffffu;
-  }
-  p.uni_modes = uni_modes_of(p.lp, L);
-  p.gather_plan = static_gather ? gather_plan_of(own, L, p.uni_modes, p.quad_mask, p.quad_far) : GATHER_RUNTIME;
-  return p;
-}
-
 void nerf_matrix_to_ngp(const float p[16], float s, float R[9], float org[3]) {
   const int rows[3] = {1, 2, 0};
   for (int r = 0; r < 3; ++r) {
@@ -502,6 +79,7 @@ struct nrf_context {
   int own_net = NET_HOT;        // the loaded model's own instance (plan_model): plan_grid checks for every grid whether it fits
   void* d_wfrag_hot = nullptr;  // fragments of the model's own register-resident instance when it is not the stage one
   GenModel gen{};  // host copy of the generic instance's description (valid unless dm.stage == NET_HOT)
+  size_t wfrag_bytes = 0, wfrag_gen_bytes = 0, wfrag_hot_bytes = 0;  // bytes of d_wfrag, d_wfrag_gen, d_wfrag_hot (nrf_debug_model_readout)
   std::vector<float> host_grid;  // the float density grid the march tables were built from
   bool grid_missing = false;     // loaded without a density grid and none generated yet
   bool allow_persistent = true;  // NRF_PERSISTENT=0 keeps the one-workgroup-per-strip render_kernel (A/B runs)
@@ -858,15 +436,18 @@ void nrf_default_options(nrf_options* o) {
 
 int nrf_level_table_compute(const nrf_model_desc* d, nrf_level_table* t) {
   if (!d || !t) return fail(NRF_E_INVALID, "null argument");
-  return compute_level_table(*d, *t);
+  const char* why = "";
+  const int rc = compute_level_table(*d, *t, why);
+  return rc ? fail(rc, why) : NRF_OK;
 }
 
 int nrf_expected_n_params(const nrf_model_desc* d, uint64_t* n) {
   if (!d || !n) return fail(NRF_E_INVALID, "null argument");
   nrf_level_table t;
-  int rc = compute_level_table(*d, t);
-  if (rc) return rc;
-  return expected_params(*d, t, *n);
+  const char* why = "";
+  int rc = compute_level_table(*d, t, why);
+  if (!rc) rc = expected_params(*d, t, *n, why);
+  return rc ? fail(rc, why) : NRF_OK;
 }
 
 int nrf_default_per_level_scale(float bound, uint32_t base_resolution, uint32_t n_levels, float* out) {
@@ -976,8 +557,9 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   if (rc) return rc;
   {
     nrf_level_table lv;
-    rc = validate_model(*d, lv);
-    if (rc) return rc;
+    const char* why = "";
+    rc = validate_model(*d, lv, why);
+    if (rc) return fail(rc, why);
   }
   HIP_TRY(hipDeviceSynchronize());  // nothing may still be reading the old model
   free_model(c);
@@ -991,66 +573,9 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
   }
   if (d->gather_copy_budget_mb) budget_mb = d->gather_copy_budget_mb;
   if (c->quad_budget_mb >= 0) budget_mb = (uint64_t)c->quad_budget_mb;
-  const ModelPlan p = plan_model(*d, c->allow_width_instances, budget_mb, c->quad_levels < 0 ? 4 : std::min(c->quad_levels, 16) / 4,
-                                     c->allow_gather_plan);
-  if (p.rc) return p.rc;
-  const nrf_level_table& lv = p.lv;
-  // fp32 -> fp16 cast of every parameter (nerf_network.h:434-436), order: density MLP | rgb MLP | grid;
-  // each MLP: first [W x in] | hidden [W x W] ... | last [16 x W] (fully_fused_mlp.cu:636-687)
-  const uint32_t F = d->n_features_per_level, L = d->n_levels, Wn = d->n_neurons;
-  const uint32_t feat_w = p.gen.feat_w, dir_w = p.gen.dir_w, rgb_in = p.gen.rgb_in;
-  struct LayerDim { uint32_t N, K, act; };
-  std::vector<LayerDim> layers;
-  auto add_mlp = [&](uint32_t in, uint32_t hidden, uint32_t act, uint32_t out_act) {
-    layers.push_back({Wn, in, act});
-    for (uint32_t i = 1; i < hidden; ++i) layers.push_back({Wn, Wn, act});
-    layers.push_back({16u, Wn, out_act});
-  };
-  add_mlp(feat_w, d->density_hidden_layers, d->density_activation, d->density_output_activation);
-  add_mlp(rgb_in, d->rgb_hidden_layers, d->rgb_activation, d->rgb_output_activation);
-  size_t n_mlp = 0;
-  for (const LayerDim& ly : layers) n_mlp += (size_t)ly.N * ly.K;
-  std::vector<_Float16> w16(n_mlp);
-  for (size_t i = 0; i < n_mlp; ++i) w16[i] = (_Float16)d->params[i];
-  const float* gp = d->params + n_mlp;
-  std::vector<_Float16> frags, frags_gen, frags_hot;
-  if (p.stage != NET_GENERIC) pack_fragments(w16, rgb_in, frags);
-  switch (p.own) {  // the fragments of a register-resident instance other than the stage one
-    case NET_W16: case NET_W32: case NET_W128: pack_fragments_width(w16, net_width(p.own), frags_hot); break;
-    case NET_DEPTH: case NET_ACT: pack_fragments_depth(w16, (int)d->density_hidden_layers, (int)d->rgb_hidden_layers, frags_hot); break;
-    case NET_WIDE_SH: pack_fragments(w16, rgb_in, frags_hot); break;  // the wide layout: first rgb layer in RK_WIDE K steps
-    case NET_GRID1: case NET_GRID2: case NET_GRID4: case NET_GRID8: pack_fragments_grid(w16, feat_w, rgb_in, F, frags_hot); break;
-    default: break;
-  }
-  // the generic description + fragments: the generic instance's model, and -- for a wide model -- what the stage
-  // entry points nrf_encode_dir / nrf_mlp_forward run on (rows of the padded widths)
-  GenModel G;
-  std::memset(&G, 0, sizeof(G));
-  if (p.stage != NET_HOT) {
-    std::vector<_Float16>& fr = p.stage == NET_GENERIC ? frags : frags_gen;
-    G = p.gen;
-    // 1: F = 2 (level_gather); 4 / 8: that F (level_gather_wide); 0: gen_level's literal index arithmetic (F = 1, Nearest, odd sizes)
-    G.fast_grid = (!p.generic_grid && (F == 2 || F == 4 || F == 8) && (d->interpolation == NRF_INTERP_LINEAR || d->interpolation == NRF_INTERP_SMOOTHSTEP) &&
-                   c->allow_gen_fast_grid) ? (F == 2 ? 1u : F) : 0u;
-    const _Float16* wp = w16.data();
-    for (size_t i = 0; i < layers.size(); ++i) {
-      G.layer[i].frag_off = (uint32_t)(fr.size() / (64 * 8));
-      G.layer[i].k_steps = (layers[i].K + 31) / 32;
-      G.layer[i].n_tiles = layers[i].N / 16;
-      G.layer[i].act = layers[i].act;
-      pack_generic_layer(wp, layers[i].N, layers[i].K, fr);
-      wp += (size_t)layers[i].N * layers[i].K;
-    }
-  }
-  // the table at the plan's level offsets (padding zero)
-  std::vector<_Float16> grid16(p.table_ref_bytes / 2, (_Float16)0.0f);
-  for (uint32_t l = 0; l < L; ++l) {
-    const LevelParams& Lv = p.lp[l];
-    const float* src = gp + (size_t)lv.offset[l] * F;
-    _Float16* dst = grid16.data() + (size_t)Lv.offset * F;
-    const size_t n = (size_t)Lv.size * F + (Lv.mode == LV_DENSE ? ((size_t)Lv.res * Lv.res + Lv.res + 1) * F : 0);
-    for (size_t i = 0; i < n; ++i) dst[i] = (_Float16)src[i % ((size_t)Lv.size * F)];
-  }
+  ModelPlan p = plan_model(*d, c->allow_width_instances, budget_mb, c->quad_levels < 0 ? 4 : std::min(c->quad_levels, 16) / 4, c->allow_gather_plan);
+  if (p.rc) return fail(p.rc, p.why);
+  const ModelImage im = build_model_image(*d, p, c->allow_gen_fast_grid);
   // Uploads go through the context's own stream and the device is drained afterwards: the
   // render stream is non-blocking, so a NULL-stream hipMemcpy gives no ordering against it
   // (seen on MI355X as a few stale table entries in the first frame after a reload).
@@ -1059,84 +584,48 @@ int nrf_load_model(nrf_context* c, const nrf_model_desc* d) {
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, c->stream);
   };
-  std::vector<LevelParams> lp(p.lp, p.lp + 16);
-  uint32_t quad_mask = p.quad_mask, quad_far = p.quad_far;
-  uint64_t table_bytes = p.table_bytes;
-  if (hipMalloc(&c->d_grid, table_bytes) != hipSuccess) {  // no room for the copies: the reference-order table alone
+  if (hipMalloc(&c->d_grid, p.table_bytes) != hipSuccess) {  // no room for the copies: the reference-order table alone
     (void)hipGetLastError();
     c->d_grid = nullptr;
-    for (LevelParams& Lv : lp) Lv.q_off_b = Lv.q_my_b = Lv.q_mz_b = Lv.q_max = 0;
-    quad_mask = quad_far = 0;
-    table_bytes = p.table_ref_bytes;
-    HIP_TRY(hipMalloc(&c->d_grid, table_bytes));
+    p = drop_quads(p);
+    HIP_TRY(hipMalloc(&c->d_grid, p.table_bytes));
   }
-  HIP_TRY(hipMemcpyAsync(c->d_grid, grid16.data(), grid16.size() * 2, hipMemcpyHostToDevice, c->stream));
-  for (uint32_t l = 0; l < L; ++l) {  // the quad copies, from the table just uploaded (same stream)
-    if (!((quad_mask >> l) & 1u)) continue;
-    const LevelParams& Lv = lp[l];
-    const uint64_t q_bytes = ((quad_far >> (l >> 2)) & 1u) ? (uint64_t)Lv.q_off_b << 4 : (uint64_t)Lv.q_off_b;
+  HIP_TRY(hipMemcpyAsync(c->d_grid, im.grid16.data(), im.grid16.size() * 2, hipMemcpyHostToDevice, c->stream));
+  for (uint32_t l = 0; l < d->n_levels; ++l) {  // the quad copies, from the table just uploaded (same stream)
+    if (!((p.quad_mask >> l) & 1u)) continue;
+    const LevelParams& Lv = p.lp[l];
+    const uint64_t q_bytes = ((p.quad_far >> (l >> 2)) & 1u) ? (uint64_t)Lv.q_off_b << 4 : (uint64_t)Lv.q_off_b;
     HIP_TRY(launch_build_quads((const char*)c->d_grid + (size_t)Lv.offset * 4, Lv.res, Lv.size, Lv.mode == LV_HASH_POW2,
                                (char*)c->d_grid + q_bytes, c->stream));
   }
-  HIP_TRY(upload(&c->d_wfrag, frags.data(), frags.size() * 2));
-  if (p.stage != NET_HOT) HIP_TRY(upload(&c->d_gen, &G, sizeof(G)));
-  if (p.stage == NET_WIDE) HIP_TRY(upload(&c->d_wfrag_gen, frags_gen.data(), frags_gen.size() * 2));
-  if (p.own != p.stage) HIP_TRY(upload(&c->d_wfrag_hot, frags_hot.data(), frags_hot.size() * 2));
-  HIP_TRY(upload(&c->d_lv, lp.data(), lp.size() * sizeof(LevelParams)));
+  HIP_TRY(upload(&c->d_wfrag, im.frags.data(), im.frags.size() * 2));
+  if (p.stage != NET_HOT) HIP_TRY(upload(&c->d_gen, &im.gen, sizeof(im.gen)));
+  if (p.stage == NET_WIDE) HIP_TRY(upload(&c->d_wfrag_gen, im.frags_gen.data(), im.frags_gen.size() * 2));
+  if (p.own != p.stage) HIP_TRY(upload(&c->d_wfrag_hot, im.frags_hot.data(), im.frags_hot.size() * 2));
+  HIP_TRY(upload(&c->d_lv, p.lp, sizeof(p.lp)));
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipDeviceSynchronize());
 
   c->desc = *d;
   c->desc.params = nullptr;
   c->desc.density_grid = nullptr;
-  c->lv = lv;
+  c->lv = p.lv;
   DevModel& M = c->dm;
-  std::memset(&M, 0, sizeof(M));
+  fill_dev_model(M, *d, p);
   M.grid = (const uint32_t*)c->d_grid;
-  M.grid_bytes = (uint32_t)std::min<uint64_t>(table_bytes, 0xffffffffull);  // (far quad copies lie beyond: no resource reads them)
   M.wfrag = (const uint4*)c->d_wfrag;
   M.lv = (const LevelParams*)c->d_lv;
-  for (int i = 0; i < 6; ++i) M.aabb[i] = d->aabb[i];
-  M.bound = d->bound;
-  M.rbound = 1.0f / d->bound;
-  M.pos_w = (float)(1.0 / (2 * (double)d->bound));
-  {
-    int e;
-    M.pos_w_pow2 = std::frexp(M.pos_w, &e) == 0.5f ? 1u : 0u;
-  }
-  M.cascade = d->cascade;
-  M.H = d->density_grid_size;
-  M.n_levels = d->n_levels;
-  M.dir_encoding = d->dir_encoding;
-  M.sh_degree = d->sh_degree;
-  M.n_frequencies = d->n_frequencies;
-  M.density_activation = d->density_activation;
-  M.density_output_activation = d->density_output_activation;
-  M.sigma_activation = d->sigma_activation;
-  M.rgb_activation = d->rgb_activation;
-  M.rgb_output_activation = d->rgb_output_activation;
-  M.uni_modes = p.uni_modes;
-  M.quad_mask = quad_mask;
-  M.quad_far = quad_far;
-  // (decided again from the copies the device had room for: without them the plan's instance would read quads that do not exist)
-  M.gather_plan = c->allow_gather_plan ? gather_plan_of(p.own, L, p.uni_modes, quad_mask, quad_far) : GATHER_RUNTIME;
-  c->table_bytes = table_bytes;
+  M.gen = (const GenModel*)c->d_gen;
+  M.wfrag_hot = (const uint4*)c->d_wfrag_hot;
+  c->table_bytes = p.table_bytes;
   c->table_ref_bytes = p.table_ref_bytes;
   c->gather_addresses = 0;
-  for (uint32_t l = 0; l < L; ++l) c->gather_addresses += ((quad_mask >> l) & 1u) ? 2u : (d->interpolation == NRF_INTERP_NEAREST ? 1u : 8u);
-  M.stage = (uint32_t)p.stage;
-  M.net = (uint32_t)p.own;  // (plan_grid falls back to the stage instance when the own one does not fit)
+  for (uint32_t l = 0; l < d->n_levels; ++l) c->gather_addresses += ((p.quad_mask >> l) & 1u) ? 2u : (d->interpolation == NRF_INTERP_NEAREST ? 1u : 8u);
   c->own_net = p.own;
-  M.gen = (const GenModel*)c->d_gen;
-  M.gen_wave_bytes = p.gen_wave_bytes;
-  M.gen_frag_bytes = p.stage == NET_GENERIC ? (uint32_t)(frags.size() * 2) : 0u;
-  M.depth_xd = (p.own == NET_DEPTH || p.own == NET_ACT) ? d->density_hidden_layers - 1 : 0u;
-  M.depth_xr = (p.own == NET_DEPTH || p.own == NET_ACT) ? d->rgb_hidden_layers - 1 : 0u;
-  M.wfrag_hot = (const uint4*)c->d_wfrag_hot;
-  M.grid_smooth = d->interpolation == NRF_INTERP_SMOOTHSTEP ? 1u : 0u;
-  M.grid_nearest = d->interpolation == NRF_INTERP_NEAREST ? 1u : 0u;
-  M.dir_w = dir_w;
-  c->gen = G;
+  c->gen = im.gen;
+  c->wfrag_bytes = im.frags.size() * 2;
+  c->wfrag_gen_bytes = im.frags_gen.size() * 2;
+  c->wfrag_hot_bytes = im.frags_hot.size() * 2;
   // the density grid of the snapshot (nerf_render.cu:447-466) -- or none yet: nrf_generate_density_grid evaluates it
   // from the network (NerfRender::generate_density_grid); until then the model cannot be rendered
   if (d->density_grid) {
@@ -1862,7 +1351,7 @@ extern "C" int nrf_debug_ray_valid(const float o[3], const float d[3]) {
 extern "C" int nrf_debug_plan(const nrf_model_desc* d, int allow_own, uint64_t budget_mb, uint32_t out[6]) {
   if (!d || !d->params || !out) return fail(NRF_E_INVALID, "null argument");
   const ModelPlan p = plan_model(*d, allow_own != 0, budget_mb, 4);
-  if (p.rc) return p.rc;
+  if (p.rc) return fail(p.rc, p.why);
   const int waves = render_persist_waves(p.own, march_form(d->density_grid_size, d->cascade, d->bound));
   const uint32_t v[6] = {(uint32_t)p.own, (uint32_t)p.stage, p.quad_mask, p.quad_far, (uint32_t)waves,
                          (uint32_t)render_persistent_lds_bytes(p.own, waves, p.gen_wave_bytes)};
@@ -1879,7 +1368,7 @@ extern "C" int nrf_debug_gather_plan(const nrf_model_desc* d, int allow_own, uin
   if (!d || !d->params || !out) return fail(NRF_E_INVALID, "null argument");
   const char* e = std::getenv("NRF_GATHER_PLAN");
   const ModelPlan p = plan_model(*d, allow_own != 0, budget_mb ? budget_mb : (uint64_t)QUAD_BUDGET_MB_DEFAULT, 4, !(e && std::atoi(e) == 0));
-  if (p.rc) return p.rc;
+  if (p.rc) return fail(p.rc, p.why);
   out[0] = p.gather_plan;
   for (int jl = 0; jl < 4; ++jl)
     out[1 + jl] = ((p.quad_mask >> (4 * jl)) & 1u) ? (((p.quad_far >> jl) & 1u) ? GFORM_QUAD_FAR : GFORM_QUAD) : ((p.uni_modes >> (2 * jl)) & 3u);
@@ -1936,12 +1425,9 @@ extern "C" int nrf_debug_grid_plan(const nrf_model_desc* d, const float* grid, f
                                    uint32_t* occ, uint32_t* coarse, float* ctab, uint32_t* dilated) {
   if (!d || !d->params || !out || !box || (!grid && !d->density_grid)) return fail(NRF_E_INVALID, "null argument");
   const ModelPlan p = plan_model(*d, (flags & 1u) != 0, QUAD_BUDGET_MB_DEFAULT, 4);
-  if (p.rc) return p.rc;
+  if (p.rc) return fail(p.rc, p.why);
   DevModel M;
-  std::memset(&M, 0, sizeof(M));
-  M.stage = (uint32_t)p.stage;
-  M.gen_wave_bytes = p.gen_wave_bytes;
-  M.gen_frag_bytes = p.stage == NET_GENERIC ? generic_frag_bytes(*d, p.gen) : 0u;
+  fill_dev_model(M, *d, p);
   const GridPlan g = plan_grid(*d, p.own, p.stage, M.gen_wave_bytes, M.gen_frag_bytes, (flags & 2u) != 0, (flags & 4u) != 0,
                                grid ? grid : d->density_grid, mean_density);
   apply_grid_plan(M, g);
@@ -1969,6 +1455,58 @@ extern "C" int nrf_debug_grid_readout(nrf_context* c, uint32_t out[17], float bo
   const void* src[4] = {c->d_occ, c->d_coarse, c->d_ctab, c->d_dilated};
   for (int i = 0; i < 4; ++i)
     if (dst[i] && c->table_words[i]) HIP_TRY(hipMemcpy(dst[i], src[i], c->table_words[i] * 4, hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// The parts of a model's image nrf_debug_model_image and nrf_debug_model_readout share (`which`): 0 frags, 1 frags_gen, 2 frags_hot,
+// 3 the GenModel bytes, 4 grid16 (the reference-order table), 5 the 16 LevelParams, 6 the plan's part of DevModel as 12 words --
+// {net, stage, quad_mask, quad_far, uni_modes, gather_plan, grid_bytes, gen_wave_bytes, gen_frag_bytes, depth_xd, depth_xr, dir_w}
+enum : int { PART_FRAGS = 0, PART_FRAGS_GEN, PART_FRAGS_HOT, PART_GEN, PART_GRID16, PART_LEVELS, PART_PLAN, N_PARTS };
+static void plan_words(const DevModel& M, uint32_t own, uint32_t out[12]) {
+  const uint32_t v[12] = {own, M.stage, M.quad_mask, M.quad_far, M.uni_modes, M.gather_plan, M.grid_bytes, M.gen_wave_bytes, M.gen_frag_bytes,
+                          M.depth_xd, M.depth_xr, M.dir_w};
+  std::memcpy(out, v, sizeof(v));
+}
+
+// Diagnostic (not part of include/nerfhip.h): one part of what nrf_load_model would upload for a descriptor, without a device --
+// plan_model at an explicit quad-copy budget (MiB; 0: QUAD_BUDGET_MB_DEFAULT, as in nrf_debug_gather_plan), then build_model_image and
+// fill_dev_model.  flags: bit 0 drop_quads first (the device had no room for the copies), bit 1 no step may have copies
+// (NRF_QUAD_LEVELS=0), bit 2 NRF_GEN_FAST_GRID=0; reads no environment.  Copies min(length, cap) bytes of part `which` to buf and
+// returns the part's length in *n (tests/test_model_image_cpu.py)
+extern "C" int nrf_debug_model_image(const nrf_model_desc* d, int allow_own, uint64_t budget_mb, uint32_t flags, int which, void* buf, uint64_t cap,
+                                     uint64_t* n) {
+  if (!d || !d->params || !n || which < 0 || which >= N_PARTS || (cap && !buf)) return fail(NRF_E_INVALID, "bad argument");
+  ModelPlan p = plan_model(*d, allow_own != 0, budget_mb ? budget_mb : (uint64_t)QUAD_BUDGET_MB_DEFAULT, (flags & 2u) ? 0 : 4);
+  if (p.rc) return fail(p.rc, p.why);
+  if (flags & 1u) p = drop_quads(p);
+  const ModelImage im = build_model_image(*d, p, (flags & 4u) == 0);
+  DevModel M;
+  fill_dev_model(M, *d, p);
+  uint32_t words[12];
+  plan_words(M, (uint32_t)p.own, words);
+  const void* src[N_PARTS] = {im.frags.data(), im.frags_gen.data(), im.frags_hot.data(), &im.gen, im.grid16.data(), p.lp, words};
+  const uint64_t len[N_PARTS] = {im.frags.size() * 2, im.frags_gen.size() * 2, im.frags_hot.size() * 2, p.stage != NET_HOT ? sizeof(GenModel) : 0,
+                                 im.grid16.size() * 2, sizeof(p.lp), sizeof(words)};
+  *n = len[which];
+  if (cap && *n) std::memcpy(buf, src[which], (size_t)std::min<uint64_t>(cap, *n));
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the same parts of the loaded context, copied back from the device (d_wfrag, d_wfrag_gen,
+// d_wfrag_hot, d_gen, the reference-order part of d_grid, d_lv; the plan's words from its DevModel) (tests/test_model_image_gpu.py)
+extern "C" int nrf_debug_model_readout(nrf_context* c, int which, void* buf, uint64_t cap, uint64_t* n) {
+  if (!c || !c->model_loaded || !n || which < 0 || which >= N_PARTS || (cap && !buf)) return fail(NRF_E_INVALID, "bad argument");
+  int rc = set_device(c);
+  if (rc) return rc;
+  uint32_t words[12];
+  plan_words(c->dm, (uint32_t)c->own_net, words);
+  const void* src[N_PARTS] = {c->d_wfrag, c->d_wfrag_gen, c->d_wfrag_hot, c->d_gen, c->d_grid, c->d_lv, words};
+  const uint64_t len[N_PARTS] = {c->wfrag_bytes, c->wfrag_gen_bytes, c->wfrag_hot_bytes, c->d_gen ? sizeof(GenModel) : 0, c->table_ref_bytes,
+                                 16 * sizeof(LevelParams), sizeof(words)};
+  *n = len[which];
+  const size_t bytes = (size_t)std::min<uint64_t>(cap, *n);
+  if (bytes && which == PART_PLAN) std::memcpy(buf, words, bytes);
+  else if (bytes) HIP_TRY(hipMemcpy(buf, src[which], bytes, hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

@@ -65,7 +65,7 @@ struct LevelParams {
 };
 static_assert(sizeof(LevelParams) == 64, "LevelParams layout");
 
-// MFMA weight fragments, packed on the host (nrf_model.cpp: pack_fragments):
+// MFMA weight fragments, packed on the host (nrf_model_plan.h: pack_fragments):
 // one fragment = 64 lanes x 8 halves (1 KiB), lane l, element j holds
 // W[16*m + (l&15)][kmap(s, l>>4, j)].
 enum : int {
@@ -131,7 +131,7 @@ struct DevModel {
                          // march tables fit beside its persistent workgroup, else `stage`)
   uint32_t stage;        // NET_HOT (the shape of the reference's base.json), NET_WIDE (the same with a Frequency direction encoding
                          // of 32..80 values) or NET_GENERIC (everything else, nrf_generic.h, described by `gen`): the instance of the
-                         // stage entry points, nrf_network, the per-strip kernel and the density-grid generation (nrf_api.hip plan_model)
+                         // stage entry points, nrf_network, the per-strip kernel and the density-grid generation (nrf_model_plan.h plan_model)
   const struct GenModel* gen;  // device memory; nullptr unless generic
   uint32_t gen_wave_bytes;     // generic instance: LDS bytes per wave of the direction rows + activation rows
   uint32_t coarse_shift;    // 2 or 0
@@ -777,7 +777,7 @@ __device__ __forceinline__ half2_t weight_times_entry(float w, uint32_t entry) {
 // fp16 accumulation in corner order (grid.h:236-262).  Returns the packed
 // half2 (feature 0 in the low half).
 //   Every level is LV_DENSE or LV_HASH_POW2 (anything else runs in the generic instance, nrf_generic.h); dense
-//   levels are stored with res^2 + res + 1 wrapped entries appended (nrf_api.hip), so `index % size` of
+//   levels are stored with res^2 + res + 1 wrapped entries appended (nrf_model_plan.h), so `index % size` of
 //   grid.h:116 needs no instruction: a dense index never exceeds size + res^2 + res.
 //   UNI: 0 = the lanes of the wave may mix dense and hashed levels (per-lane select);
 //        1 = every lane's level is dense, 2 = every lane's level is power-of-two hashed.
@@ -1190,7 +1190,7 @@ __device__ __forceinline__ half8_t dir_entries8(uint32_t nf, uint32_t e0, float 
 // Lane l = (g = l>>4, c = l&15) holds sample c of each tile.  A layer's D
 // fragment (lane holds outs 16m+4g+r) is re-packed in-lane as the next
 // layer's B fragment; the K permutation this implies is baked into the weight
-// fragments (pack_fragments), so no activation ever crosses lanes or LDS.
+// fragments (nrf_model_plan.h pack_fragments), so no activation ever crosses lanes or LDS.
 __device__ __forceinline__ float4_t mfma16(half8_t a, half8_t b, float4_t c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }

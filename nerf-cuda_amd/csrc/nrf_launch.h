@@ -9,7 +9,7 @@
 namespace nrf {
 // Instances of the render kernel (nrf_render.h), one id for host and device code.  DevModel::net renders the frames;
 // DevModel::stage (NET_HOT, NET_WIDE or NET_GENERIC) runs the stage entry points, the per-strip kernel and the density-grid
-// generation, and renders the frames when the model's own instance does not fit (nrf_api.hip plan_model, plan_grid).
+// generation, and renders the frames when the model's own instance does not fit (nrf_model_plan.h plan_model, nrf_api.hip plan_grid).
 // NET_W16 / NET_W32 / NET_W128: the register-resident instance for the other widths of tcnn's FullyFusedMLP (persistent kernel only)
 // NET_WIDE_SH: the wide form for SphericalHarmonics of degree 5..8 (32..64 direction values): the entries beyond the first sixteen
 // are computed once per ray into an LDS row (not per sample in-lane as for Frequency) -- persistent kernel only
@@ -30,7 +30,7 @@ __host__ __device__ constexpr int net_width(int net) { return net == NET_W16 ? 1
 // uni_modes (gather_step); a static plan names the four forms, so that the tile program has no control flow between a sample's
 // loads -- behind the run-time diamonds the compiler drains the memory counter in front of every step but the first
 // (profiles/r07/gather_plan_listing.txt).  Static plans exist for the NET_HOT persistent kernel only (nrf_kernels_hot_*.hip);
-// plan_model (nrf_api.hip: gather_plan_of) picks one when the model's steps have exactly its forms.
+// plan_model (nrf_model_plan.h: gather_plan_of) picks one when the model's steps have exactly its forms.
 enum : uint32_t { GFORM_MIXED = 0, GFORM_DENSE = 1, GFORM_HASHED = 2, GFORM_QUAD = 3, GFORM_QUAD_FAR = 4 };  // (0..2: uni_modes' values)
 __host__ __device__ constexpr uint32_t gather_plan(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t f3) {
   return 0x10000u | f0 | (f1 << 4) | (f2 << 8) | (f3 << 12);

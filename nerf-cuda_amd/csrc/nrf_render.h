@@ -105,10 +105,10 @@ __device__ __forceinline__ unsigned long long stamp_rt() {
 // SHROWS (NET_WIDE_SH): those entries come from the ray's LDS row instead (rows = the wave's rows, SH_ROW_HALVES apart).
 // The lane's 8 grid features (4 dwords) of a GRID instance: lane group g encodes the levels {g, 4 + g, ...} it can hold -- 4 levels
 // of F = 2, 2 of F = 4, 1 of F = 8 -- features in tcnn's order level-major; levels the grid does not have are zero (the padding of
-// the grid encoding is ZERO, grid.h:959-969).  K order of the first density layer: nrf_api.hip pack_fragments_grid.
+// the grid encoding is ZERO, grid.h:959-969).  K order of the first density layer: nrf_model_plan.h kmap_levels.
 // DENS (the RAYS_DENSITY instances): sigma alone -- no read of dirf, rayd or rows, mlp_tiles<.., DENS>, no store of W->out[slot].xyz.
 // F = 1 (NET_GRID1, round 5): lane group g holds the ONE feature of each of its levels {g, 4 + g, 8 + g, 12 + g} -- four halves, the
-// lane's other four features are zero columns (feat_w = 16: pack_fragments_grid) --, two levels to a dword, two levels in flight.
+// lane's other four features are zero columns (feat_w = 16: kmap_levels) --, two levels to a dword, two levels in flight.
 __device__ __forceinline__ void grid_features_f1(const DevModel& M, const LevelParams* lvs, float px, float py, float pz, int g, uint32_t (&fb)[4]) {
 #pragma unroll
   for (int j0 = 0; j0 < 4; j0 += 2) {
@@ -244,7 +244,7 @@ __device__ __forceinline__ void gather_step_static(const DevModel& M, const Leve
   else level_gather<0>(M.grid, M.grid_bytes, L, px, py, pz, v, fr);
 }
 // words of level l's block: quad forms {scale, q_off_b, q_my_b, q_mz_b} (the far form's q_max is q_my_b - 1: both are functions
-// of res, nrf_api.hip), hashed {scale, off_b, mask_b, -}, dense and mixed {scale, off_b, my_b, mz_b}, mixed also {mask_b, mode, -, -}
+// of res, nrf_model_plan.h), hashed {scale, off_b, mask_b, -}, dense and mixed {scale, off_b, my_b, mz_b}, mixed also {mask_b, mode, -, -}
 static_assert(MARCH_GENERIC == MARCH_FORM_GENERIC && MARCH_UNIT == MARCH_FORM_UNIT && MARCH_POW2 == MARCH_FORM_POW2, "plan_frag_depth's march form");
 static_assert(LDS_LEVEL_BYTES >= 16 * 32, "the staged plan levels live in the level table's region");
 template <uint32_t GP>
