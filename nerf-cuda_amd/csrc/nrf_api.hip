@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "nrf_device.h"
+#include "nrf_frame_plan.h"
 #include "nrf_generic.h"
 #include "nrf_grid_plan.h"
 #include "nrf_launch.h"
@@ -209,14 +210,6 @@ void free_frame(nrf_context* c) {
   c->rendered = false;
 }
 
-int total_strips(int W, int H) { return ((((W + 7) / 8) + 3) / 4) * ((H + 7) / 8); }
-
-int local_tiles(int W, int H, int shard_index, int shard_count) {
-  const int total = total_strips(W, H);
-  if (shard_index >= total) return 0;
-  return 4 * ((total - shard_index + shard_count - 1) / shard_count);
-}
-
 // the shard layout (tile-major [n_tiles][64]) instead of the row-major frame: every multi-shard render, and a single shard on request
 bool tiled_layout(const nrf_context* c) { return c->opt.shard_count > 1 || c->opt.tile_major != 0; }
 
@@ -224,9 +217,7 @@ int alloc_frame(nrf_context* c) {
   if (c->W <= 0 || c->H <= 0) return NRF_OK;
   const bool tiled = tiled_layout(c);
   c->n_local_tiles = local_tiles(c->W, c->H, c->opt.shard_index, c->opt.shard_count);
-  int tps = 0;
-  nrf_tiles_per_shard(c->W, c->H, c->opt.shard_count, &tps);
-  const size_t per_view = tiled ? (size_t)tps * 64 : (size_t)c->W * c->H;
+  const size_t per_view = tiled ? (size_t)tiles_per_shard(c->W, c->H, c->opt.shard_count) * 64 : (size_t)c->W * c->H;
   const size_t need = per_view * (size_t)c->max_views;
   if (per_view == c->n_out_px && need == c->n_alloc_px && c->d_rgba) return NRF_OK;
   HIP_TRY(hipDeviceSynchronize());
@@ -247,8 +238,8 @@ int fill_frame_params(nrf_context* c, const float cam[4], const float pose[16], 
   for (int i = 0; i < 4; ++i) P.cam[i] = cam[i];
   P.W = c->W;
   P.H = c->H;
-  P.tiles_x = (c->W + 7) / 8;
-  P.tiles_y = (c->H + 7) / 8;
+  P.tiles_x = tiles_of(c->W);
+  P.tiles_y = tiles_of(c->H);
   P.shard_index = c->opt.shard_index;
   P.shard_count = c->opt.shard_count;
   P.n_local_tiles = c->n_local_tiles;
@@ -271,49 +262,6 @@ int fill_frame_params(nrf_context* c, const float cam[4], const float pose[16], 
   P.fast_interp = c->opt.fast_interp ? 1 : 0;
   P.queue_classes = c->queue_classes;
   return NRF_OK;
-}
-
-// Pixel rectangle outside of which no ray of the view can enter `box` (the inflated box of occupied cells,
-// NGP coordinates): the bounding rectangle of the projections of its 8 corners, 3 pixels wider on every side;
-// the whole image when a corner is not safely in front of the camera; empty when the box is.  Conservative
-// by construction: the box is convex, so a ray that enters it passes through the convex hull of the projected
-// corners; rays inside the rectangle still take the exact per-ray slab test in the kernel.
-void view_roi(const float R[9], const float org[3], const float cam[4], const float box[6], int W, int H, int roi[4]) {
-  roi[0] = 0; roi[1] = 0; roi[2] = W - 1; roi[3] = H - 1;
-  if (!(box[0] <= box[3])) {  // no occupied cell at all
-    roi[2] = -1;
-    roi[3] = -1;
-    return;
-  }
-  // camera coordinates of a world offset p: v = R^-1 p (ray_dir applies R to the camera-space direction; poses
-  // need not be orthonormal, so the inverse is computed, not assumed to be the transpose)
-  const double a = R[0], b = R[1], cc = R[2], d = R[3], e = R[4], f = R[5], g = R[6], h = R[7], i = R[8];
-  const double det = a * (e * i - f * h) - b * (d * i - f * g) + cc * (d * h - e * g);
-  if (!(std::fabs(det) > 1e-12)) return;
-  const double inv[9] = {(e * i - f * h) / det, (cc * h - b * i) / det, (b * f - cc * e) / det,
-                         (f * g - d * i) / det, (a * i - cc * g) / det, (cc * d - a * f) / det,
-                         (d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det};
-  double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
-  for (int c = 0; c < 8; ++c) {
-    const double p[3] = {(double)box[(c & 1) ? 3 : 0] - org[0], (double)box[(c & 2) ? 4 : 1] - org[1],
-                         (double)box[(c & 4) ? 5 : 2] - org[2]};
-    const double vx = inv[0] * p[0] + inv[1] * p[1] + inv[2] * p[2];
-    const double vy = inv[3] * p[0] + inv[4] * p[1] + inv[5] * p[2];
-    const double vz = inv[6] * p[0] + inv[7] * p[1] + inv[8] * p[2];
-    if (!(vz > 1e-3)) return;  // corner beside / behind the camera (or NaN): keep the whole image
-    const double u = cam[2] + cam[0] * vx / vz, v = cam[3] + cam[1] * vy / vz;
-    if (!(u == u) || !(v == v)) return;
-    lo[0] = u < lo[0] ? u : lo[0]; hi[0] = u > hi[0] ? u : hi[0];
-    lo[1] = v < lo[1] ? v : lo[1]; hi[1] = v > hi[1] ? v : hi[1];
-  }
-  // pixel (i, j) looks through (i + 0.5, j + 0.5)
-  const double m = 3.0;
-  const double x0 = std::floor(lo[0] - 0.5 - m), y0 = std::floor(lo[1] - 0.5 - m);
-  const double x1 = std::ceil(hi[0] - 0.5 + m), y1 = std::ceil(hi[1] - 0.5 + m);
-  roi[0] = x0 < 0 ? 0 : (x0 > W ? W : (int)x0);
-  roi[1] = y0 < 0 ? 0 : (y0 > H ? H : (int)y0);
-  roi[2] = x1 < -1 ? -1 : (x1 > W - 1 ? W - 1 : (int)x1);
-  roi[3] = y1 < -1 ? -1 : (y1 > H - 1 ? H - 1 : (int)y1);
 }
 
 // The grid side of the plan (nrf_grid_plan.h), decided without a device like plan_model (nrf_debug_grid_plan:
@@ -459,7 +407,7 @@ int nrf_default_per_level_scale(float bound, uint32_t base_resolution, uint32_t 
 
 int nrf_tiles_per_shard(int width, int height, int shard_count, int* n) {
   if (!n || width <= 0 || height <= 0 || shard_count <= 0) return fail(NRF_E_INVALID, "bad argument");
-  *n = 4 * ((total_strips(width, height) + shard_count - 1) / shard_count);
+  *n = tiles_per_shard(width, height, shard_count);
   return NRF_OK;
 }
 
@@ -731,30 +679,6 @@ int nrf_set_max_views(nrf_context* c, int max_views) {
 }  // extern "C"
 
 namespace {
-// the rows [lo, hi) of a frame that the strip rows of a view's region of interest cover (what launch_render queues for the
-// persistent kernel); every pixel outside them is the background
-void roi_rows(const int roi[4], int H, int& lo, int& hi) {
-  lo = hi = 0;
-  if (roi[2] < roi[0] || roi[3] < roi[1]) return;
-  const int tiles_y = (H + 7) / 8;
-  const int ty0 = std::max(roi[1] >> 3, 0), ty1 = std::min(roi[3] >> 3, tiles_y - 1);
-  if (ty1 < ty0) return;
-  lo = 8 * ty0;
-  hi = std::min(H, 8 * (ty1 + 1));
-}
-
-// the columns [x0, x1) of whole tiles a view's region of interest touches: the tiles beside them are background (the kernel tests
-// every tile's 8x8 pixels against the region)
-void roi_cols(const int roi[4], int W, int& x0, int& x1) {
-  x0 = x1 = 0;
-  if (roi[2] < roi[0] || roi[3] < roi[1]) return;
-  const int tiles_x = (W + 7) / 8;
-  const int tx0 = std::max(roi[0] >> 3, 0), tx1 = std::min(roi[2] >> 3, tiles_x - 1);
-  if (tx1 < tx0) return;
-  x0 = 8 * tx0;
-  x1 = std::min(W, 8 * (tx1 + 1));
-}
-
 // One launch per NRF_MAX_VIEWS cameras; all launches of a call go to the same stream back to back.  Every call takes the
 // next slot of the context's ring of statistics counters + work queues (cleared on the call's own stream), so calls of
 // one context that overlap on different streams never share a queue.
@@ -796,25 +720,12 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
   const DevModel dm = rays ? rays_model(c) : c->dm;
   P.out_mode = out_mode;
   P.skip_outside = skip_outside;
-  // one or two views alone are latency-bound, not throughput-bound: their last tiles end sooner when every ray queues its full
-  // eight samples per round, and the few samples evaluated for nothing cost nobody anything (0.904 against 0.914 ms per 1080p view)
-  // ... unless the launch has fewer tiles than the chip has waves: it is ALL tail (idle waves take rays off the rendering ones from
-  // the first round on, and every split group queues its own eight samples per ray behind a terminating one) -- small frames
-  // keep the transmittance-dependent queue, which holds their evaluated samples within 15 % of the composited ones
-  // (tests/test_parity_gpu.py, test_generic_gpu.py, test_golden.py; pixels cannot depend on it: tests/test_persistent_gpu.py)
-  const bool all_tail = (long long)c->n_local_tiles * n_views < (long long)dm.n_cus * std::max(1u, dm.persist_waves);
-  if (n_views <= 2 && !c->sample_cap_forced && !all_tail) P.sample_cap = 0;
+  if (drops_sample_cap(c->n_local_tiles, n_views, (int)dm.n_cus, dm.persist_waves, c->sample_cap_forced)) P.sample_cap = 0;  // (nrf_frame_plan.h)
   c->call_index = (c->call_index + 1) % CALL_RING;
   char* counters = call_slot(c, c->call_index);
   unsigned* plan = (c->plan_max_pos > 0 && prog == nullptr && rays == nullptr) ? (unsigned*)((char*)c->d_plan + (size_t)c->call_index * PLAN_BYTES) : nullptr;
   HIP_TRY(hipEventRecord(c->ev0, st));  // (render_ms covers the clearing of the call's counters and the planning of its queues)
-  // views per launch: NRF_MAX_VIEWS, fewer when the frames are so large that the persistent kernel's 24-bit queue positions
-  // (strip rows of all views x strips per row) would not hold the launch (8K frames: 64 views)
-  int per_launch = MAX_VIEWS;
-  {
-    const long long per_view = (long long)P.tiles_y * ((P.tiles_x + 3) / 4);
-    if (per_view * per_launch >= 0xffffff) per_launch = (int)std::max(1LL, 0xfffffeLL / std::max(per_view, 1LL));
-  }
+  const int per_launch = views_per_launch(P.tiles_x, P.tiles_y, MAX_VIEWS);  // NRF_MAX_VIEWS, fewer for frames beyond 8K
   const size_t px_bytes_a = out_mode == OUT_U8 ? 3 : 16, px_bytes_b = out_mode == OUT_U8 ? 1 : 4;
   for (int first = 0; first < n_views; first += per_launch) {
     ViewBatch VB;
@@ -839,17 +750,7 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
       nerf_matrix_to_ngp(poses + 16 * (size_t)(first + v), c->desc.scale, VB.v[v].R, VB.v[v].org);
       for (int i = 0; i < 4; ++i) VB.v[v].cam[i] = cams[4 * (size_t)(first + v) + i];
       view_roi(VB.v[v].R, VB.v[v].org, VB.v[v].cam, c->dm.occ_box, c->W, c->H, VB.v[v].roi);
-      {
-        // A camera thousands of scene sizes away: t + dt == t in fp32 once t passes ~2^24 dt (dt_min = 0.0034: t ~ 5.7e4), the
-        // march of render_utils.h:593-653 stops advancing and never ends (the reference hangs there; so would this kernel).
-        // Long before that the object is far below a pixel: such a view is background (an empty region of interest).
-        const float* o = VB.v[v].org;
-        const float far2 = o[0] * o[0] + o[1] * o[1] + o[2] * o[2];
-        if (!(far2 <= MAX_CAMERA_DISTANCE * MAX_CAMERA_DISTANCE)) {
-          VB.v[v].roi[0] = VB.v[v].roi[1] = 0;
-          VB.v[v].roi[2] = VB.v[v].roi[3] = -1;
-        }
-      }
+      far_camera_roi(VB.v[v].org, MAX_CAMERA_DISTANCE, VB.v[v].roi);
       if (rows_out) {  // {row lo, row hi, column lo, column hi} per view
         int* ro = rows_out + 4 * (size_t)(first + v);
         roi_rows(VB.v[v].roi, c->H, ro[0], ro[1]);
@@ -970,39 +871,19 @@ int nrf_render_rays(nrf_context* c, int n_views, const void* rays_o, const void*
 // context owns, and the rows outside it -- background by construction -- are filled by the calling thread while the GPU
 // renders (only those that held something else: a camera that moves a little costs a few rows).  Two slots: the copy of
 // one call overlaps the render of the next.
-static uint8_t host_quant_u8(float v) {  // quant_u8 of nrf_render.h
-  const double s = 255.0 * (double)v;
-  if (!(s > 0.0)) return 0;
-  if (s >= 255.0) return 255;
-  return (uint8_t)s;
-}
-
 namespace {
 // copies the rows [lo, hi) of view v of a host-frame slot (both planes) on the context's copy stream; x0 < x1: only the
 // columns [x0, x1) of those rows (a pitched copy: scripts/copy2d_probe.py measured 46.5 GB/s for 80 % of a 1080p frame's width
 // against 49.1 GB/s for whole rows -- 0.85 of the time)
 int copy_rows(nrf_context* c, nrf_context::HostSlot& h, int v, int lo, int hi, int x0 = 0, int x1 = 0) {
   if (hi <= lo) return NRF_OK;
-  const size_t Wb = (size_t)h.W, px = h.px, depth_off = h.views * px * 3;
-  const bool cols = x1 > x0 && (x0 > 0 || x1 < h.W);
-  const size_t ro = ((size_t)v * px + (size_t)lo * Wb) * 3, rn = (size_t)(hi - lo) * Wb * 3;
-  const size_t dofs = depth_off + (size_t)v * px + (size_t)lo * Wb, dn = (size_t)(hi - lo) * Wb;
-  if (cols) {
-    const size_t wpx = (size_t)(x1 - x0), n_rows = (size_t)(hi - lo);
-    HIP_TRY(hipMemcpy2DAsync(h.h_buf + ro + (size_t)x0 * 3, Wb * 3, (const uint8_t*)h.d_buf + ro + (size_t)x0 * 3, Wb * 3, wpx * 3, n_rows,
-                             hipMemcpyDeviceToHost, c->copy_stream));
-    h.copied += wpx * 3 * n_rows;
-    if (h.with_depth) {
-      HIP_TRY(hipMemcpy2DAsync(h.h_buf + dofs + x0, Wb, (const uint8_t*)h.d_buf + dofs + x0, Wb, wpx, n_rows, hipMemcpyDeviceToHost, c->copy_stream));
-      h.copied += wpx * n_rows;
-    }
-    return NRF_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(h.h_buf + ro, (const uint8_t*)h.d_buf + ro, rn, hipMemcpyDeviceToHost, c->copy_stream));
-  h.copied += rn;
-  if (h.with_depth) {
-    HIP_TRY(hipMemcpyAsync(h.h_buf + dofs, (const uint8_t*)h.d_buf + dofs, dn, hipMemcpyDeviceToHost, c->copy_stream));
-    h.copied += dn;
+  const RowCopy k = row_copy(h.W, h.px, h.views, v, lo, hi, x0, x1);
+  const uint8_t* d_buf = (const uint8_t*)h.d_buf;
+  for (const PlaneCopy* p : {&k.rgb, &k.depth}) {
+    if (p == &k.depth && !h.with_depth) break;
+    if (k.pitched) HIP_TRY(hipMemcpy2DAsync(h.h_buf + p->off, p->pitch, d_buf + p->off, p->pitch, p->width, p->rows, hipMemcpyDeviceToHost, c->copy_stream));
+    else HIP_TRY(hipMemcpyAsync(h.h_buf + p->off, d_buf + p->off, p->width, hipMemcpyDeviceToHost, c->copy_stream));
+    h.copied += p->bytes();
   }
   return NRF_OK;
 }
@@ -1012,30 +893,8 @@ int copy_rows(nrf_context* c, nrf_context::HostSlot& h, int v, int lo, int hi, i
 // stores, acknowledged before the row was counted -- nrf_render.h tile_written); whatever is left when the kernel's end
 // event fires is copied then.  The loop ends with the kernel at the latest: it cannot wait for a flag that never comes.
 int progressive_copies(nrf_context* c, nrf_context::HostSlot& h) {
-  struct Band { int view, lo, hi, s0, s1; };  // pixel rows [lo, hi) = strip rows [s0, s1) of the view
-  std::vector<Band> bands;
-  const int tiles_y = (h.H + 7) / 8;
-  // ~16 bands per call (one view alone: bands of ~70 rows at 1080p; a batch of 16 views: one band per view), but no copy
-  // below 64 KiB: the runtime moves smaller ones with a blit KERNEL, which gets no compute unit while the persistent render
-  // is resident -- it, and every copy queued behind it, would wait for the render's end (scripts/copy_overlap_probe2.py:
-  // 16 KiB copies issued during a 13 ms render all ended with it, 64 KiB ones ran beside it).  The smallest copy of a band
-  // is its depth plane (W bytes per row; rgb-only frames: 3 W).
-  long total = 0;
-  for (int v = 0; v < h.n_views; ++v) total += (h.rows[4 * v + 1] + 7) / 8 - h.rows[4 * v] / 8;
-  const long want_rows = std::max(4L, (total + 15) / 16);  // strip rows per band
-  const long row_bytes = (long)h.W * (h.with_depth ? 1 : 3);
-  const long min_rows = (65536 + 8 * row_bytes - 1) / (8 * row_bytes);  // strip rows whose smallest plane is 64 KiB
-  for (int v = 0; v < h.n_views; ++v) {
-    const int lo = h.rows[4 * v], hi = h.rows[4 * v + 1];
-    if (hi <= lo) continue;
-    const long s_lo = lo / 8, s_hi = (hi + 7) / 8, n = s_hi - s_lo;
-    const long per = std::max(want_rows, min_rows);
-    const long n_bands = std::max(1L, n / per);  // (the remainder is spread over the bands: none is smaller than `per`)
-    for (long b = 0; b < n_bands; ++b) {
-      const int s0 = (int)(s_lo + n * b / n_bands), s1 = (int)(s_lo + n * (b + 1) / n_bands);
-      bands.push_back({v, std::max(lo, 8 * s0), std::min(hi, 8 * s1), s0, s1});
-    }
-  }
+  std::vector<Band> bands = plan_bands(h.W, h.with_depth, h.n_views, h.rows.data());  // (nrf_frame_plan.h)
+  const int tiles_y = tiles_of(h.H);
   // A copy costs the engine ~12 us before its first byte moves (a 550 KB band: 34 us for 10 us of link time), and the rows of
   // a frame rendered alone complete within the last tenth of its render: band by band the copies ran for 0.3 ms after the
   // kernel's end.  So ready bands are issued in GROUPS: adjacent ones merged into one copy per plane, at most two groups in
@@ -1130,7 +989,7 @@ int nrf_submit_host_u8(nrf_context* c, int n_views, const float* cams, const flo
   if (h.pending && h.copies_issued) HIP_TRY(hipEventSynchronize(h.done));
   h.pending = false;
   const size_t px = (size_t)c->W * c->H;
-  const int tiles_y = (c->H + 7) / 8;
+  const int tiles_y = tiles_of(c->H);
   // keyed on the frame's GEOMETRY, not its pixel count: 1920x1080 -> 1080x1920 keeps W * H but changes the row bookkeeping
   // (row_lo / row_hi / bg describe byte ranges of the old width) and the number of strip rows (d_done / h_flags entries)
   if (h.px != px || h.W != c->W || h.H != c->H || h.views < (size_t)n_views) {
@@ -1165,18 +1024,8 @@ int nrf_submit_host_u8(nrf_context* c, int n_views, const float* cams, const flo
   h.copied = 0;
   h.copies_issued = false;
   // progress reporting needs the persistent form of the kernel (launch_render's choice for this model)
-  h.progressive = c->host_progressive && c->dm.persistent && c->dm.lds_coarse_words > 0;
-  {
-    // A launch whose queue order is PLANNED (one or two views: dearest strips first, nrf_kernels.hip "queue planning") completes
-    // its rows within the last tenth of the render -- nothing to copy meanwhile, and copies that are already queued behind the
-    // render's event start sooner than ones the waiting thread issues when it sees the flags (one 1080p view: 1.09 against
-    // 1.14 ms per call; three views and more, which are not planned: 2.54 against 2.98 the other way round)
-    // ... and two views gain next to nothing from the plan on the device (1.64 against 1.67 ms) while it costs their host end
-    // the progressive copies (2.00 against 1.82 ms per call): only a frame rendered alone is planned here, every larger call
-    // keeps the queue order of its views and copies them as they complete (render_views_impl: no plan with progress reporting)
-    const long strips = (long)n_views * tiles_y * ((c->W + 31) / 32);
-    if (n_views == 1 && c->plan_max_pos > 0 && strips <= (long)c->plan_max_pos) h.progressive = false;
-  }
+  // ... and a frame rendered alone, whose launch is planned, copies after its render (nrf_frame_plan.h)
+  h.progressive = host_frame_progressive(c->host_progressive && c->dm.persistent && c->dm.lds_coarse_words > 0, n_views, c->W, tiles_y, c->plan_max_pos);
   const size_t depth_off = h.views * px * 3;  // depth planes follow the rgb planes of ALL views the slot holds
   h.rows.assign((size_t)4 * n_views, 0);
   ProgressArgs prog{h.d_done, h.h_flags, 0u};
@@ -1210,7 +1059,6 @@ int nrf_submit_host_u8(nrf_context* c, int n_views, const float* cams, const flo
     const bool all = h.bg != bg;
     const size_t Wb = (size_t)c->W;
     auto fill = [&](int v, int r0, int r1, int c0, int c1) {
-      if (r1 <= r0 || c1 <= c0) return;
       if (c0 == 0 && c1 == c->W) {
         std::memset(h.h_buf + ((size_t)v * px + (size_t)r0 * Wb) * 3, bg, (size_t)(r1 - r0) * Wb * 3);
         std::memset(h.h_buf + depth_off + (size_t)v * px + (size_t)r0 * Wb, 0, (size_t)(r1 - r0) * Wb);  // depth of a missed ray: 0
@@ -1224,23 +1072,12 @@ int nrf_submit_host_u8(nrf_context* c, int n_views, const float* cams, const flo
     const bool use_cols = c->host_cols && !h.progressive;  // (what this call's copies write: the region's columns, or whole rows)
     for (int v = 0; v < (int)h.views; ++v) {
       if (v < n_views) {
-        const int lo = h.rows[4 * v], hi = h.rows[4 * v + 1];
-        int x0 = use_cols ? h.rows[4 * v + 2] : 0, x1 = use_cols ? h.rows[4 * v + 3] : c->W;
-        if (x1 <= x0) { x0 = 0; x1 = c->W; }
-        const int plo = all ? 0 : h.row_lo[v], phi = all ? c->H : h.row_hi[v];
-        const int pc0 = all ? 0 : h.col_lo[v], pc1 = all ? c->W : h.col_hi[v];
-        if (hi <= lo) fill(v, plo, phi, pc0, pc1);
-        else {
-          fill(v, plo, std::min(phi, lo), pc0, pc1);
-          fill(v, std::max(plo, hi), phi, pc0, pc1);
-          const int m0 = std::max(plo, lo), m1 = std::min(phi, hi);  // the rows both rectangles share: the columns beside the new one
-          fill(v, m0, m1, pc0, std::min(pc1, x0));
-          fill(v, m0, m1, std::max(pc0, x1), pc1);
-        }
-        h.row_lo[v] = lo;
-        h.row_hi[v] = hi;
-        h.col_lo[v] = x0;
-        h.col_hi[v] = x1;
+        const FillPlan F = fill_rects({h.row_lo[v], h.row_hi[v], h.col_lo[v], h.col_hi[v]}, all, c->W, c->H, &h.rows[4 * v], use_cols);
+        for (int i = 0; i < F.n; ++i) fill(v, F.rects[i].r0, F.rects[i].r1, F.rects[i].c0, F.rects[i].c1);
+        h.row_lo[v] = F.now.r0;
+        h.row_hi[v] = F.now.r1;
+        h.col_lo[v] = F.now.c0;
+        h.col_hi[v] = F.now.c1;
       } else if (all) {  // (not part of this call: stays as it is, counted as unknown)
         h.row_lo[v] = 0;
         h.row_hi[v] = c->H;
@@ -1441,6 +1278,92 @@ extern "C" int nrf_debug_grid_plan(const nrf_model_desc* d, const float* grid, f
   if (coarse) std::memcpy(coarse, T.coarse.data(), T.coarse.size() * 4);
   if (ctab) std::memcpy(ctab, T.ctab.data(), T.ctab.size() * 4);
   if (dilated) std::memcpy(dilated, T.dilated.data(), T.dilated.size() * 4);
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the frame plan (nrf_frame_plan.h) of one render call, without a context or a device.
+// in = {W, H, shard_index, shard_count, n_views, n_cus, persist_waves, queue_classes, plan_max_pos, plan_cap, dilated bytes, flags,
+// the previous rectangle of the fill {row lo, row hi, column lo, column hi}, RENDER_WAVES}; flags: 1 sample cap forced, 2 depth
+// plane, 4 host_cols, 8 the context and model allow progressive copies, 16 the launch has a plan buffer and a dilated table, 32 the
+// fill's background changed, 64 one launch of up to NRF_MAX_VIEWS views whatever views_per_launch says (the refusal), 128 a host
+// frame: bands, copies and fills follow.  fin = {model scale, background, occupied box[6]}; rois (optional): the views' regions
+// [n_views][4] instead of cams [n_views][4] / poses [n_views][16].  out = 24 values {tiles_x, tiles_y, strips per row, strips,
+// local tiles, tiles per shard, views per launch, all_tail, sample cap dropped, progressive, views of the first launch, q_total,
+// n_classes, class_cols, workgroups, blocks_per_view, refused, planned, n_pos, copied bytes, bands, fill rectangles, filled
+// bytes, the quantised background}, per view {roi[4], row lo, row hi, column lo, column hi}, per view of the first launch
+// {k_lo, k_hi, q_begin, q_rows, q_row0}; a host frame: per band {view, lo, hi, s0, s1}, per view {pitched, rgb off, pitch,
+// width, rows, depth off, pitch, width, rows}, per view {n, 4 x {r0, r1, c0, c1}, the new rectangle} (tests/test_frame_plan_cpu.py)
+extern "C" int nrf_debug_frame_plan(const int32_t in[17], const float fin[8], const float* cams, const float* poses, const int32_t* rois,
+                                    int64_t* out, int64_t cap, int64_t* n_out) {
+  if (!in || !fin || !out || !n_out || (!rois && (!cams || !poses))) return fail(NRF_E_INVALID, "null argument");
+  const int W = in[0], H = in[1], idx = in[2], N = in[3], n_views = in[4], n_cus = in[5], waves = in[6], flags = in[11];
+  if (W < 1 || H < 1 || N < 1 || idx < 0 || idx >= N || n_views < 1 || n_cus < 1 || waves < 1 || in[16] < 1) return fail(NRF_E_INVALID, "bad argument");
+  const bool host = (flags & 128) != 0, with_depth = (flags & 2) != 0;
+  std::vector<int64_t> o(24, 0);
+  const int tiles_x = tiles_of(W), tiles_y = tiles_of(H), n_local = local_tiles(W, H, idx, N);
+  const int per_launch = views_per_launch(tiles_x, tiles_y, MAX_VIEWS);
+  const int launch_views = std::min(n_views, (flags & 64) ? MAX_VIEWS : per_launch);
+  const bool progressive = host_frame_progressive((flags & 8) != 0, n_views, W, tiles_y, in[8]);
+  std::vector<int> roi((size_t)4 * n_views), rows((size_t)4 * n_views);
+  for (int v = 0; v < n_views; ++v) {
+    int* r = &roi[4 * (size_t)v];
+    if (rois) std::memcpy(r, rois + 4 * (size_t)v, 4 * sizeof(int));
+    else {
+      float R[9], org[3];
+      nerf_matrix_to_ngp(poses + 16 * (size_t)v, fin[0], R, org);
+      view_roi(R, org, cams + 4 * (size_t)v, fin + 2, W, H, r);
+      far_camera_roi(org, MAX_CAMERA_DISTANCE, r);
+    }
+    int* ro = &rows[4 * (size_t)v];
+    roi_rows(r, H, ro[0], ro[1]);
+    roi_cols(r, W, ro[2], ro[3]);
+    o.insert(o.end(), r, r + 4);
+    o.insert(o.end(), ro, ro + 4);
+  }
+  std::vector<ViewQueue> vq((size_t)launch_views);
+  const QueuePlan Q = plan_queues({tiles_x, tiles_y, idx, N, n_local, in[7], n_cus, waves, in[16]}, launch_views, roi.data(), vq.data());
+  for (const ViewQueue& q : vq) o.insert(o.end(), {q.k_lo, q.k_hi, q.q_begin, q.q_rows, q.q_row0});
+  int64_t copied = 0, n_bands = 0, n_fill = 0, filled = 0;
+  if (host) {
+    auto put = [&](const PlaneCopy& p, bool on) { o.insert(o.end(), {on ? (int64_t)p.off : 0, on ? (int64_t)p.pitch : 0, on ? (int64_t)p.width : 0, on ? (int64_t)p.rows : 0}); };
+    const std::vector<Band> bands = progressive ? plan_bands(W, with_depth, n_views, rows.data()) : std::vector<Band>();
+    n_bands = (int64_t)bands.size();
+    const size_t px = (size_t)W * H;
+    for (const Band& b : bands) {
+      o.insert(o.end(), {b.view, b.lo, b.hi, b.s0, b.s1});
+      const RowCopy k = row_copy(W, px, (size_t)n_views, b.view, b.lo, b.hi, 0, 0);
+      copied += (int64_t)(k.rgb.bytes() + (with_depth ? k.depth.bytes() : 0));
+    }
+    const bool use_cols = (flags & 4) && !progressive;
+    for (int v = 0; v < n_views; ++v) {
+      const int* ro = &rows[4 * (size_t)v];
+      const bool on = !progressive && ro[1] > ro[0];
+      const RowCopy k = on ? row_copy(W, px, (size_t)n_views, v, ro[0], ro[1], use_cols ? ro[2] : 0, use_cols ? ro[3] : 0) : RowCopy{};
+      o.push_back(k.pitched ? 1 : 0);
+      put(k.rgb, on);
+      put(k.depth, on && with_depth);
+      if (on) copied += (int64_t)(k.rgb.bytes() + (with_depth ? k.depth.bytes() : 0));
+    }
+    for (int v = 0; v < n_views; ++v) {
+      const FillPlan F = fill_rects({in[12], in[13], in[14], in[15]}, (flags & 32) != 0, W, H, &rows[4 * (size_t)v], use_cols);
+      o.push_back(F.n);
+      for (int i = 0; i < 4; ++i) {
+        const Rect r = i < F.n ? F.rects[i] : Rect{0, 0, 0, 0};
+        o.insert(o.end(), {r.r0, r.r1, r.c0, r.c1});
+        filled += 4LL * (r.r1 - r.r0) * (r.c1 - r.c0);  // (rgb + depth bytes)
+      }
+      o.insert(o.end(), {F.now.r0, F.now.r1, F.now.c0, F.now.c1});
+      n_fill += F.n;
+    }
+  }
+  const int64_t head[24] = {tiles_x, tiles_y, strips_per_row(tiles_x), total_strips(W, H), n_local, tiles_per_shard(W, H, N), per_launch,
+                            call_is_all_tail(n_local, n_views, n_cus, (unsigned)waves), drops_sample_cap(n_local, n_views, n_cus, (unsigned)waves, (flags & 1) != 0),
+                            progressive, launch_views, Q.q_total, Q.n_classes, Q.class_cols, Q.workgroups, Q.blocks_per_view, Q.refused,
+                            launch_is_planned((flags & 16) != 0, Q.n_pos, in[9], in[10]), Q.n_pos, copied, n_bands, n_fill, filled, host_quant_u8(fin[1])};
+  std::copy(head, head + 24, o.begin());
+  *n_out = (int64_t)o.size();
+  if ((int64_t)o.size() > cap) return fail(NRF_E_INVALID, "the output buffer is too small");
+  std::copy(o.begin(), o.end(), out);
   return NRF_OK;
 }
 
@@ -1676,9 +1599,7 @@ int nrf_untile_views_u8(nrf_context* c, const void* gathered_rgbd8, int shard_co
     return fail(NRF_E_INVALID, "the gathered shards must be 16-byte aligned, the 8-bit planes 4-byte aligned (widths that are multiples of 4)");
   int rc = set_device(c);
   if (rc) return rc;
-  int tps = 0;
-  nrf_tiles_per_shard(c->W, c->H, shard_count, &tps);
-  if (tps != tiles_per_shard) return fail(NRF_E_INVALID, "tiles_per_shard does not match the resolution");
+  if (tiles_per_shard != nrf::tiles_per_shard(c->W, c->H, shard_count)) return fail(NRF_E_INVALID, "tiles_per_shard does not match the resolution");
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   HIP_TRY(launch_untile_rgbd8_u8(gathered_rgbd8, shard_count, tiles_per_shard, c->W, c->H, n_views, rgb8, depth8, st));
   if (!stream) HIP_TRY(hipStreamSynchronize(st));
@@ -1692,9 +1613,7 @@ int nrf_untile_views(nrf_context* c, const void* gathered, int shard_count, int 
   if (c->W <= 0) return fail(NRF_E_STATE, "set_resolution has not been called");
   int rc = set_device(c);
   if (rc) return rc;
-  int tps = 0;
-  nrf_tiles_per_shard(c->W, c->H, shard_count, &tps);
-  if (tps != tiles_per_shard) return fail(NRF_E_INVALID, "tiles_per_shard does not match the resolution");
+  if (tiles_per_shard != nrf::tiles_per_shard(c->W, c->H, shard_count)) return fail(NRF_E_INVALID, "tiles_per_shard does not match the resolution");
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   HIP_TRY(launch_untile(gathered, shard_count, tiles_per_shard, channels, c->W, c->H, n_views, out, st));
   if (!stream) HIP_TRY(hipStreamSynchronize(st));

@@ -162,7 +162,7 @@ struct ViewParams {
   float org[3];  // translation
   float cam[4];  // fl_x, fl_y, cx, cy
   int roi[4];    // x0, y0, x1, y1 (pixels, inclusive): no ray outside this rectangle enters the box of occupied
-                 // cells (host: conservative projection of its corners, nrf_api.hip view_roi); x1 < x0: empty
+                 // cells (host: conservative projection of its corners, nrf_frame_plan.h view_roi); x1 < x0: empty
   // persistent kernel: the local tiles [k_lo, k_hi) (multiples of 4 = whole strips) cover the q_rows strip rows (from row q_row0) the
   // rectangle touches; those rows are units [q_begin, q_begin + q_rows) of the launch's work queues; the view's other
   // tiles are background and are filled without the queues

@@ -4,6 +4,9 @@
 // "stage entry points"), the planning kernels, the pixel-format kernels and every launcher.  The render kernel itself is a
 // template in nrf_render.h; its instances are compiled in nrf_kernels_{hot,width,wide,generic,strip}.hip.
 
+#include <cstring>
+
+#include "nrf_frame_plan.h"
 #include "nrf_render.h"
 
 namespace nrf {
@@ -765,7 +768,7 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
   P.plan_order = nullptr;
   // the call's statistics counters and queue words are zero before its first launch (plan_price_kernel does it for a planned launch)
   auto clear_for_first = [&]() { return first_launch ? hipMemsetAsync(counters, 0, COUNTER_BYTES + RENDER_QUEUE_BYTES, st) : hipSuccess; };
-  VB.blocks_per_view = (P.n_local_tiles + RENDER_WAVES - 1) / RENDER_WAVES;
+  VB.blocks_per_view = blocks_per_view(P.n_local_tiles, RENDER_WAVES);
   if (VB.blocks_per_view <= 0 || VB.n_views <= 0) return clear_for_first();  // a shard without a strip (tiny frames, many ranks)
   if (VB.n_views > MAX_VIEWS) return hipErrorInvalidValue;
   const int blocks = VB.blocks_per_view * VB.n_views;
@@ -778,44 +781,32 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
   if (rays && (perturb || P.rays_d == nullptr || (M.persistent && M.net != NET_HOT))) return hipErrorInvalidValue;
   if (rays) plan = nullptr;
   if (M.persistent && lds_tab) {
-    // work queues: per view the strip rows its region of interest touches (sharded: the local strips of those rows)
-    const int strips_x = (P.tiles_x + 3) >> 2, N = P.shard_count, idx = P.shard_index;
-    const int k_end = (P.n_local_tiles + 3) & ~3;
-    int q = 0;
+    // work queues: per view the strip rows its region of interest touches (nrf_frame_plan.h plan_queues)
+    int rois[MAX_VIEWS][4];
+    ViewQueue vq[MAX_VIEWS];
+    for (int v = 0; v < VB.n_views; ++v) std::memcpy(rois[v], VB.v[v].roi, sizeof(rois[v]));
+    const int waves = (int)M.persist_waves;
+    const QueuePlan Q = plan_queues({P.tiles_x, P.tiles_y, P.shard_index, P.shard_count, P.n_local_tiles, P.queue_classes, (int)M.n_cus, waves, RENDER_WAVES},
+                                    VB.n_views, &rois[0][0], vq);
     for (int v = 0; v < VB.n_views; ++v) {
       ViewParams& V = VB.v[v];
-      V.k_lo = V.k_hi = 0;
-      int rows = 0, row0 = 0;
-      if (V.roi[2] >= V.roi[0] && V.roi[3] >= V.roi[1]) {
-        const int ty0 = std::max(V.roi[1] >> 3, 0), ty1 = std::min(V.roi[3] >> 3, P.tiles_y - 1);
-        if (ty1 >= ty0) {
-          rows = ty1 - ty0 + 1;
-          row0 = ty0;
-          const int s0 = ty0 * strips_x, s1 = (ty1 + 1) * strips_x;  // global strips [s0, s1)
-          const int ls0 = s0 > idx ? (s0 - idx + N - 1) / N : 0, ls1 = s1 > idx ? (s1 - idx + N - 1) / N : 0;
-          V.k_lo = std::min(4 * ls0, k_end);
-          V.k_hi = std::min(4 * ls1, k_end);
-        }
-      }
-      V.q_begin = q;
-      V.q_rows = rows;
-      V.q_row0 = row0;
-      q += rows;  // units: the strip rows the region of interest touches
+      V.k_lo = vq[v].k_lo;
+      V.k_hi = vq[v].k_hi;
+      V.q_begin = vq[v].q_begin;
+      V.q_rows = vq[v].q_rows;
+      V.q_row0 = vq[v].q_row0;
     }
-    VB.q_total = q;
-    VB.n_classes = P.queue_classes >= 1 && P.queue_classes <= 8 ? P.queue_classes : 8;
-    VB.class_cols = (strips_x + N - 1) / N;  // a row holds at most this many of the rank's strips
-    if ((long long)q * VB.class_cols >= 0xffffff) return hipErrorInvalidValue;  // 24-bit queue positions
-    const int waves = (int)M.persist_waves;
+    VB.q_total = Q.q_total;
+    VB.n_classes = Q.n_classes;
+    VB.class_cols = Q.class_cols;
+    if (Q.refused) return hipErrorInvalidValue;  // 24-bit queue positions
     const int lds = render_persistent_launch_lds_bytes(M);
-    const long long tiles = (long long)P.n_local_tiles * VB.n_views;
-    const int wgs = (int)std::max(1LL, std::min((long long)M.n_cus, (tiles + waves - 1) / waves));
+    const int wgs = Q.workgroups;
     unsigned* queue = reinterpret_cast<unsigned*>((unsigned long long*)counters + COUNTER_SLOTS * 16);
     hipError_t e = hipSuccess;
-    const long long n_pos = (long long)q * VB.class_cols;
+    const long long n_pos = Q.n_pos;
     const size_t dil_bytes = (size_t)4 * M.dilated_level_words * M.cascade;
-    if (first_launch && plan != nullptr && M.occ_dilated != nullptr && n_pos > 0 && n_pos <= (long long)plan_cap && n_pos <= 60 * 1024 &&
-        dil_bytes <= 60 * 1024) {
+    if (launch_is_planned(first_launch && plan != nullptr && M.occ_dilated != nullptr, n_pos, plan_cap, (long long)dil_bytes)) {
       const int blocks = (int)((n_pos * 4 + PLAN_THREADS - 1) / PLAN_THREADS);
       hipLaunchKernelGGL(plan_price_kernel, dim3(blocks), dim3(PLAN_THREADS), (dil_bytes + 15) & ~(size_t)15, st, M, P, VB, plan,
                          (unsigned*)counters, (unsigned)((COUNTER_BYTES + RENDER_QUEUE_BYTES) / 4));

@@ -837,7 +837,7 @@ def test_single_shard_in_the_shard_layout(ctx):
 @pytest.mark.parametrize("radius,az,el,fl_scale", [(0.9, 40, 10, 1.0), (0.3, 200, 35, 0.4), (2.2, 310, 80, 3.0), (1.5, 0, -89, 1.0)])
 def test_region_of_interest_cull_is_conservative(ctx, small, radius, az, el, fl_scale):
     """The per-view pixel rectangle outside of which strips are filled with the background without
-    generating rays (nrf_api.hip view_roi): cameras inside the volume, next to the box of occupied
+    generating rays (nrf_frame_plan.h view_roi): cameras inside the volume, next to the box of occupied
     cells (corners behind the image plane -> whole image), far away with a long lens (object spans
     the frame), looking straight up -- the frame must still match the oracle everywhere."""
     desc, keep, o = small
