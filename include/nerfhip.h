@@ -347,6 +347,30 @@ typedef struct nrf_rays {
   uint32_t reserved; /* = 0 */
 } nrf_rays;
 int nrf_render_rays_clipped(nrf_context* ctx, int n_views, const nrf_rays* rays, void* stream, nrf_frame* out);
+/* (ABI 7, addition) Ray hits: where a caller's ray reaches an opacity threshold -- picking, collision and placement, range
+ * sensors, the origins of the shadow rays NRF_RAYS_DENSITY_ONLY serves.  A ray is processed exactly as nrf_render_rays_clipped
+ * with NRF_RAYS_DENSITY_ONLY processes it -- the guard, near / far and the clamp by t_min / t_max, the march, the density network,
+ * density_scale, and per sample  alpha,  T = 1 - ws,  w = alpha * T,  ws += w,  dep += w * t  -- with one more termination: after a
+ * sample's update, ws >= opacity (an fp32 compare on the updated ws) ends the ray; that sample counts as composited.  The
+ * ordinary terminations (T < 1e-4, t >= far, max_steps) stay.  The crossing sample is the first whose updated ws reaches opacity.
+ *                 hit                                          miss (never reached opacity)   no ray / refused / empty interval
+ *   rgba[..][0]   t of the crossing sample as composited: the   0                              0
+ *                 end of its interval, what dep += w * t uses
+ *   rgba[..][1]   the crossing sample's dt                      0                              0
+ *   rgba[..][2]   ws before the crossing sample (< opacity)     0                              0
+ *   rgba[..][3]   ws after it (>= opacity)                      the final ws (< opacity)       0
+ *   depth         the sum of w * t up to and including the      that sum over the whole ray    0
+ *                 crossing sample (NRF_RAYS_DEPTH_T semantics)
+ * A hit is recognised by rgba[..][3] >= opacity.  bg_color and backgrounds play no part.  Refinement: if density is constant inside
+ * the crossing sample, the exact crossing distance is
+ *     t* = t - dt + dt * ln((1 - a0) / (1 - opacity)) / ln((1 - a0) / (1 - a1)),    a0 = rgba[..][2], a1 = rgba[..][3];
+ * the kernel does not compute it.
+ * rays->rays_o, rays_d, rays_per_view, t_min, t_max: as nrf_render_rays_clipped.  rays->background must be NULL, rays->flags and
+ * rays->reserved 0, and 0 < opacity <= 1 (NaN is invalid): NRF_E_INVALID otherwise.  An 8-bit output bound (nrf_bind_output_rgbd8 /
+ * _u8): NRF_E_UNSUPPORTED, nothing is written.  perturb > 0: NRF_E_UNSUPPORTED.  fast_interp is ignored.  Everything else is as in
+ * nrf_render_rays_clipped: views, shards and tile_major, bound float outputs, nrf_set_max_views, stream rules, the 16 calls in
+ * flight, nrf_get_stats (a ray that stops at the threshold stops marching: n_composited counts what it composited), nrf_read_*. */
+int nrf_ray_hits(nrf_context* ctx, int n_views, const nrf_rays* rays, float opacity, void* stream, nrf_frame* out);
 /* Binds caller-owned device buffers (e.g. a render buffer's RGBA plane or a
  * torch tensor) as the target of subsequent nrf_render calls: rgba float
  * [n_px][4], depth float [n_px], n_px as nrf_frame describes.  NULL, NULL

@@ -697,6 +697,7 @@ struct RayArgs {
   // nrf_render_rays_clipped (nullptr / 0: nrf_render_rays): per-ray limits of t [n_views][per_view], per-ray background [..][3], nrf_rays.flags
   const float *t_min = nullptr, *t_max = nullptr, *background = nullptr;
   uint32_t flags = 0;
+  float hit_opacity = 0.f;  // nrf_ray_hits: > 0 = the launch is a hit launch with this threshold (0: every other call)
 };
 // The model as the RAYS instances see it: the persistent form for the hot shape only (GridFit::rays_persistent); the per-strip
 // kernel borrows the weight area for the dilated table, so it is given what fits there (GridFit::lds_dilated_strip)
@@ -745,6 +746,12 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
       P.ray_tmax = rays->t_max ? rays->t_max + (size_t)first * rays->per_view : nullptr;
       P.ray_bg = rays->background ? rays->background + 3 * (size_t)first * rays->per_view : nullptr;
       P.ray_flags = rays->flags;
+      if (rays->hit_opacity > 0.f) {  // nrf_ray_hits: the RAYS_HIT instances; no background takes part, a pixel nobody renders is zero
+        P.ray_flags = RAY_FLAG_HIT | RAY_FLAG_DEPTH_T;
+        P.hit_opacity = rays->hit_opacity;
+        P.hit_exp = hit_cap_exponent(rays->hit_opacity);  // (nrf_frame_plan.h)
+        P.bg_color = 0.f;
+      }
     }
     for (int v = 0; !rays && v < VB.n_views; ++v) {
       nerf_matrix_to_ngp(poses + 16 * (size_t)(first + v), c->desc.scale, VB.v[v].R, VB.v[v].org);
@@ -852,6 +859,25 @@ int nrf_render_rays_clipped(nrf_context* c, int n_views, const nrf_rays* r, void
   rays.t_max = (const float*)r->t_max;
   rays.background = (const float*)r->background;
   rays.flags = r->flags;
+  return render_frames(c, n_views, nullptr, nullptr, &rays, stream, out);
+}
+
+int nrf_ray_hits(nrf_context* c, int n_views, const nrf_rays* r, float opacity, void* stream, nrf_frame* out) {
+  static const float none[16] = {};
+  int rc = check_renderable(c, none, none, n_views);
+  if (rc) return rc;
+  if (!r || !r->rays_o || !r->rays_d) return fail(NRF_E_INVALID, "null argument");
+  if (r->reserved != 0 || r->flags != 0 || r->background != nullptr)
+    return fail(NRF_E_INVALID, "nrf_ray_hits: nrf_rays.flags and reserved must be 0 and background NULL");
+  if (!(opacity > 0.0f && opacity <= 1.0f)) return fail(NRF_E_INVALID, "nrf_ray_hits: opacity must be in (0, 1]");  // (NaN fails both)
+  if (r->rays_per_view < 1 || r->rays_per_view > (uint64_t)c->W * (uint64_t)c->H)
+    return fail(NRF_E_INVALID, "rays_per_view must be 1 .. width * height of nrf_set_resolution");
+  if (c->opt.perturb > 0) return fail(NRF_E_UNSUPPORTED, "nrf_render_rays has no perturb instances (nrf_options.perturb must be 0)");
+  if (c->bound_rgbd8 || c->bound_rgb8) return fail(NRF_E_UNSUPPORTED, "nrf_ray_hits needs float planes: an 8-bit output is bound");
+  RayArgs rays{(const float*)r->rays_o, (const float*)r->rays_d, r->rays_per_view};
+  rays.t_min = (const float*)r->t_min;
+  rays.t_max = (const float*)r->t_max;
+  rays.hit_opacity = opacity;
   return render_frames(c, n_views, nullptr, nullptr, &rays, stream, out);
 }
 
@@ -1366,6 +1392,10 @@ extern "C" int nrf_debug_frame_plan(const int32_t in[17], const float fin[8], co
   std::copy(o.begin(), o.end(), out);
   return NRF_OK;
 }
+
+// Diagnostic (not part of include/nerfhip.h): FrameParams::hit_exp of an nrf_ray_hits call with this threshold (hit_cap_exponent,
+// nrf_frame_plan.h), without a context or a device (tests/test_ray_hits_cpu.py)
+extern "C" int nrf_debug_hit_cap_exponent(float opacity) { return hit_cap_exponent(opacity); }
 
 // Diagnostic (not part of include/nerfhip.h): the same 17 values of the loaded context, its occ_box, and its four device tables
 // copied to the buffers that are given (tests/test_grid_plan_gpu.py)

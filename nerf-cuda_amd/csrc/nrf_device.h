@@ -237,6 +237,11 @@ struct FrameParams {
   const float* ray_tmin;
   const float* ray_tmax;
   const float* ray_bg;
+  // nrf_ray_hits (the RAYS_HIT instances alone read these; 0 in every other launch): a ray stops at the first sample whose updated
+  // weight sum is >= hit_opacity.  hit_exp: the binary exponent of 1 - hit_opacity (hit_cap_exponent, nrf_frame_plan.h), by which the
+  // per-round sample queue sizes itself for T <= 1 - hit_opacity instead of T < 1e-4; -13 (hit_opacity == 1): the rule of sample_cap == 2.
+  float hit_opacity;
+  int hit_exp;
 };
 constexpr unsigned RAY_FLAG_DEPTH_T = 1u;  // == NRF_RAYS_DEPTH_T
 // == NRF_RAYS_DENSITY_ONLY (bit 1 stays unassigned).  The host reads it to pick the launch's instances (nrf_kernels_rays.hip); no
@@ -245,7 +250,14 @@ constexpr unsigned RAY_FLAG_DENSITY_ONLY = 4u;
 // The RAYS template argument of tile_rounds, render_kernel and render_persistent_kernel (nrf_render.h): where an instance's rays
 // come from and what it evaluates for a sample.  RAYS_DENSITY: the density network alone -- no direction encoding, no colour
 // network, no colour sums; alpha, depth and the statistics are those of RAYS_FULL bit for bit, rgb is the transmitted background.
-constexpr int RAYS_NONE = 0, RAYS_FULL = 1, RAYS_DENSITY = 2;
+// RAYS_HIT (nrf_ray_hits): RAYS_DENSITY that also stops a ray at the first sample whose updated weight sum reaches
+// FrameParams::hit_opacity, and stores that sample's record where the colour would go (tile_rounds, finish_pixel: nrf_render.h).
+constexpr int RAYS_NONE = 0, RAYS_FULL = 1, RAYS_DENSITY = 2, RAYS_HIT = 3;
+// the modes that evaluate the density network alone: no direction encoding, no colour network, no colour sums
+__host__ __device__ constexpr bool rays_density_like(int rays) { return rays == RAYS_DENSITY || rays == RAYS_HIT; }
+// Internal, from the high bits of FrameParams::ray_flags (no value of nrf_rays.flags reaches them: the entry points refuse unknown
+// bits): the launch is nrf_ray_hits' -- the ray launchers hand it to the RAYS_HIT instances, nrf_kernels_rays_hit.hip.
+constexpr unsigned RAY_FLAG_HIT = 0x80000000u;
 
 // ------------------------------------------------------------- ray guard ----
 // The march of render_utils.h:593-653 never ends once t + dt == t in fp32: with dt_min = 0.0034 that is t ~ 2^24 dt ~ 5.7e4 (the

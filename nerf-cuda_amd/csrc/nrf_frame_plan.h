@@ -195,6 +195,19 @@ inline bool call_is_all_tail(int n_local_tiles, int n_views, int n_cus, unsigned
 inline bool drops_sample_cap(int n_local_tiles, int n_views, int n_cus, unsigned persist_waves, bool forced) {
   return n_views <= 2 && !forced && !call_is_all_tail(n_local_tiles, n_views, n_cus, persist_waves);
 }
+// nrf_ray_hits (FrameParams::hit_exp): a ray stops once its weight sum is >= opacity, that is at T <= 1 - opacity, so the per-round
+// queue of sample_cap == 2 holds what the ray needs to get THERE if every sample halves T: clamp(exponent(T) - hit_cap_exponent, 1, 8),
+// with the frexp exponent of the fp32 difference 1 - opacity (0.5 -> 0, 0.9 -> -3, 0.99 -> -6, nextafter(1, 0) -> -23).
+// Like the rule for T < 1e-4 it compares exponents and ignores the two mantissas: the queue can be one halving short of the need,
+// never more (host/hit_cap_asan.cpp).  Pixels cannot depend on it, only the samples evaluated behind a ray's last one.
+// opacity == 1 (the difference is 0 and has no exponent) and anything outside (0, 1) keep today's rule, -13: T < 1e-4 = 2^-13.3.
+constexpr int SAMPLE_CAP_EXPONENT = -13;
+inline int hit_cap_exponent(float opacity) {
+  if (!(opacity > 0.0f && opacity < 1.0f)) return SAMPLE_CAP_EXPONENT;
+  int e = 0;
+  (void)std::frexp(1.0f - opacity, &e);
+  return std::max(e, SAMPLE_CAP_EXPONENT);  // (no threshold asks for more samples than the ordinary termination allows)
+}
 
 // Whether a host frame's copies are progressive (issued by the waiting thread as the kernel flags strip rows) -- capable: the
 // context allows it and the model renders in the persistent kernel with its tables in LDS.

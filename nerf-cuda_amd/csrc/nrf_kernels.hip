@@ -1064,6 +1064,7 @@ void preload_kernels(bool all) {
     preload_grid();
     preload_rays();
     preload_rays_density();
+    preload_rays_hit();
   }
 }
 

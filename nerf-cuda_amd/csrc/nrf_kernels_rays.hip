@@ -10,7 +10,7 @@
 //   per-strip wide   UNIT: R C;  POW2: F (wide-pow2);  GENERIC, tables in LDS: F (wide-h96);  in global memory: F (wide-h30)
 //   per-strip generic   tables in LDS: R C (without a limit), F (sine-h96);  in global memory: F (sine-h30)
 // NRF_RAYS_DENSITY_ONLY (FrameParams::ray_flags & RAY_FLAG_DENSITY_ONLY): the two launchers hand the launch to the density-only twins
-// of these instances, nrf_kernels_rays_density.hip.
+// of these instances, nrf_kernels_rays_density.hip; nrf_ray_hits (RAY_FLAG_HIT): to the twins of those, nrf_kernels_rays_hit.hip.
 // (one family of render-kernel instances per translation unit: nrf_render.h)
 #include "nrf_render.h"
 
@@ -33,6 +33,7 @@ namespace nrf {
 
 hipError_t launch_persistent_rays(const PersistLaunch& L) {
   if (L.M->net != NET_HOT || L.P->rays_o == nullptr || L.P->rays_d == nullptr) return hipErrorInvalidConfiguration;
+  if (L.P->ray_flags & RAY_FLAG_HIT) return launch_persistent_rays_hit(L);
   if (L.P->ray_flags & RAY_FLAG_DENSITY_ONLY) return launch_persistent_rays_density(L);
   if (L.unit) NRF_LAUNCH_HOT_RAYS(MARCH_UNIT);
   else if (L.pow2) NRF_LAUNCH_HOT_RAYS(MARCH_POW2);
@@ -50,6 +51,7 @@ hipError_t launch_persistent_rays(const PersistLaunch& L) {
 
 hipError_t launch_strip_rays(const StripLaunch& L) {
   if (L.perturb || L.P->rays_o == nullptr || L.P->rays_d == nullptr) return hipErrorInvalidConfiguration;
+  if (L.P->ray_flags & RAY_FLAG_HIT) return launch_strip_rays_hit(L);
   if (L.P->ray_flags & RAY_FLAG_DENSITY_ONLY) return launch_strip_rays_density(L);
   if (L.M->stage == NET_GENERIC) {
     if (L.lds_tab) NRF_LAUNCH_RENDER_RAYS(NET_GENERIC, true, MARCH_GENERIC); else NRF_LAUNCH_RENDER_RAYS(NET_GENERIC, false, MARCH_GENERIC);

@@ -805,6 +805,9 @@ __device__ __forceinline__ uint32_t ray_number(const FrameParams& P, uint32_t pi
 // RAYS is RAYS_NONE, RAYS_FULL or RAYS_DENSITY (nrf_device.h).  RAYS_DENSITY: the network phase evaluates sigma alone and cr, cg, cb
 // stay what they came in as (0; they travel in the tail-split mail as such); ws, dep, n_comp, the termination test and `alive` are
 // those of RAYS_FULL, from the same instructions on the same sigma.
+// RAYS_HIT (nrf_ray_hits): RAYS_DENSITY with one more termination -- the first sample whose updated ws is >= P.hit_opacity ends the ray
+// and leaves its record in cr, cg, cb (composited t, dt, ws before it).  Nothing else is written per sample, so the three are 0 for as
+// long as a ray lives: the tail-split mail carries them as such and its layout is RAYS_DENSITY's (registers: DESIGN.md "Ray hits").
 template <int NET, bool COARSE_LDS, int MARCH, bool HELP = false, bool FAST = false, bool PERTURB = false, int RAYS = RAYS_NONE,
           uint32_t GP = GATHER_RUNTIME>
 __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams& P, const MarchConst& mc, const LdsMap& lm,
@@ -894,7 +897,8 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
     else if (P.sample_cap == 2) {  // the samples the ray still needs to reach T < 1e-4 (= 2^-13.3) if every one of them halves T
       int e;
       (void)__builtin_frexpf(Tq, &e);
-      cap = min(max(e + 13, 1), 8);
+      if constexpr (RAYS == RAYS_HIT) cap = min(max(e - P.hit_exp, 1), 8);  // ... to reach T <= 1 - hit_opacity (hit_cap_exponent, nrf_frame_plan.h)
+      else cap = min(max(e + 13, 1), 8);
     }
     for (int k = 0; k < 8; ++k) {
       const unsigned long long mm = __ballot(marching);
@@ -949,7 +953,7 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
 
     if (S > 0) {
       // ---- network on the S queued samples (sample-major MFMA tiles)
-      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH), RAYS == RAYS_DENSITY>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
+      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH), rays_density_like(RAYS)>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
       wave_sync();
     }
     NRF_STAMP(t2);
@@ -965,14 +969,18 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
         const float alpha = 1.0f - __expf(-so.w * dtc.x);
         const float T = 1 - ws;
         const float wgt = alpha * T;
+        [[maybe_unused]] const float ws_before = ws;  // (RAYS_HIT; dead in every other instance)
         ws += wgt;
         dep += wgt * dtc.y;  // depth += weight * t, t = composited t of this sample
-        if constexpr (RAYS != RAYS_DENSITY) {
+        if constexpr (!rays_density_like(RAYS)) {
           cr += wgt * so.x;
           cg += wgt * so.y;
           cb += wgt * so.z;
         }
         n_comp++;
+        if constexpr (RAYS == RAYS_HIT) {  // the crossing sample: its composited t, its dt, ws before it
+          if (ws >= P.hit_opacity) { cr = dtc.y; cg = dtc.x; cb = ws_before; terminated = true; break; }
+        }
         // `T < 1e-4` against a double literal: true exactly for T <= 9.99999974737875e-05f
         if (T <= 9.99999974737875e-05f) { terminated = true; break; }
       }
@@ -1043,9 +1051,16 @@ __device__ __forceinline__ void clamp_ray(const FrameParams& P, int view, uint32
 // RAYS: `listed` = the pixel has a ray in the caller's arrays (number rn of view `view`) -- such a pixel is composited over its own
 // entry of FrameParams::ray_bg when there is one (12 bytes, read here and carried nowhere), every other over the scalar bg_color;
 // RAY_FLAG_DEPTH_T: the depth is acc.dep as composited, not normalised.
-template <bool RAYS>
+// HIT (the RAYS_HIT instances): the pixel is the ray's record as tile_rounds left it -- (t, dt, ws before, ws after) of the crossing
+// sample, (0, 0, 0, final ws) of a ray that never reached the threshold, zeros without a ray -- and the depth is acc.dep as
+// composited: no background term, no normalisation.
+template <bool RAYS, bool HIT = false>
 __device__ __forceinline__ float4 finish_pixel(const FrameParams& P, const TileAcc& acc, float near, float far, int view, uint32_t rn,
                                                bool listed, float& dn) {
+  if constexpr (HIT) {
+    dn = acc.dep;
+    return make_float4(acc.cr, acc.cg, acc.cb, acc.ws);
+  }
   const float span = far - near;
   dn = span > 0.0f ? fmaxf(acc.dep - near, 0.0f) / span : 0.0f;
   if constexpr (RAYS) {
@@ -1070,7 +1085,8 @@ __device__ __forceinline__ float4 finish_pixel(const FrameParams& P, const TileA
 // slowest tile is done.
 // (the generic instance is bound by its LDS rows, not by registers: no 128-VGPR cap there)
 // RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray) -- instances of their own, nrf_kernels_rays.hip;
-// RAYS_DENSITY (NRF_RAYS_DENSITY_ONLY): their twins without direction encoding and colour network, nrf_kernels_rays_density.hip
+// RAYS_DENSITY (NRF_RAYS_DENSITY_ONLY): their twins without direction encoding and colour network, nrf_kernels_rays_density.hip;
+// RAYS_HIT (nrf_ray_hits): the twins of those that stop at an opacity threshold, nrf_kernels_rays_hit.hip
 template <int NET, bool COARSE_LDS, int MARCH, bool PERTURB = false, int RAYS = RAYS_NONE>
 __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NET_WIDE ? 3 : 4)) void render_kernel(const DevModel M, const FrameParams P, const ViewBatch VB,
                                                      float4* __restrict__ rgba, float* __restrict__ depth,
@@ -1242,7 +1258,7 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
       }
 #endif
     }
-    if (RAYS != RAYS_DENSITY && alive) {  // direction encoding: only rays that will evaluate the colour network need it
+    if (!rays_density_like(RAYS) && alive) {  // direction encoding: only rays that will evaluate the colour network need it
       float u0 = 0.5f * d[0]; u0 = u0 + 0.5f;  // linear_transformer(0.5, 0.5), nerf_render.cu:313-314
       float u1 = 0.5f * d[1]; u1 = u1 + 0.5f;
       float u2 = 0.5f * d[2]; u2 = u2 + 0.5f;
@@ -1295,7 +1311,7 @@ __global__ __launch_bounds__(RENDER_THREADS, NET == NET_GENERIC ? 2 : (NET == NE
   {
     const uint32_t rn = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
     float dn;
-    const float4 c = finish_pixel<RAYS != RAYS_NONE>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
+    const float4 c = finish_pixel<RAYS != RAYS_NONE, RAYS == RAYS_HIT>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
     store_pixel(P, rgba, depth, k_local, lane, px, py, in_img, c, dn);
   }
   counters += (blockIdx.x % COUNTER_SLOTS) * 16;  // see COUNTER_SLOTS
@@ -1415,7 +1431,8 @@ static_assert(offsetof(PersistArgs, P) == (sizeof(DevModel) + alignof(FrameParam
 // FAST: nrf_options::fast_interp (opt-in single-rounding interpolation; register-resident instance only) -- instances of
 // their own, so that the shipped default symbols keep the bit-exact arithmetic (tests/test_abi_cpu.py checks their ISA)
 // RAYS (nrf_render_rays): the rays come from the caller's arrays (load_ray; every view's region of interest is its whole frame) --
-// instances of their own, nrf_kernels_rays.hip; RAYS_DENSITY: their density-only twins, nrf_kernels_rays_density.hip.
+// instances of their own, nrf_kernels_rays.hip; RAYS_DENSITY: their density-only twins, nrf_kernels_rays_density.hip; RAYS_HIT:
+// the twins of those for nrf_ray_hits, nrf_kernels_rays_hit.hip.
 // (FAST stays the last argument: tests/test_abi_cpu.py reads it off the symbol names)
 // GP: the gather plan (nrf_launch.h) -- GATHER_RUNTIME, or one of the static plans of the hot instance (nrf_kernels_hot_*.hip)
 template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false, bool U8 = false, int RAYS = RAYS_NONE,
@@ -1661,7 +1678,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     bool given = false;  // tail splitting: this lane's ray went to a helper wave, which stores its pixel
     const uint32_t pix_idx = P.tile_major ? (uint32_t)k_local * 64u + (uint32_t)lane : (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
     if (__ballot(alive) != 0ull) {
-      if (RAYS != RAYS_DENSITY && alive) encode_ray_dir<NET>(M, lm, lane, d);  // direction encoding of the rays that will evaluate the colour network
+      if (!rays_density_like(RAYS) && alive) encode_ray_dir<NET>(M, lm, lane, d);  // direction encoding of the rays that will evaluate the colour network
       wave_sync();
       NRF_STAMP(t_setup_done);
       const HelpArgs ha = {hl, lm.W - wave, view};
@@ -1680,7 +1697,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     // ---- get_image_and_depth (finish_pixel)
     float dn;
     const uint32_t rn = (uint32_t)py * (uint32_t)P.W + (uint32_t)px;
-    const float4 c = finish_pixel<RAYS != RAYS_NONE>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
+    const float4 c = finish_pixel<RAYS != RAYS_NONE, RAYS == RAYS_HIT>(P, acc, near, far, view, rn, in_img && rn < P.rays_per_view, dn);
 #ifdef NRF_PHASE_TIMING
     if (P.march_budget == 4095) {  // diagnostic: the depth plane carries the tile's cost (cycles / 1e6) and start time instead
       NRF_STAMP(t_tile_end);
@@ -1780,7 +1797,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const int sx = __builtin_signbitf(d[0]) ? 0 : 1;
     const int sy = __builtin_signbitf(d[1]) ? 0 : 1;
     const int sz = __builtin_signbitf(d[2]) ? 0 : 1;
-    if (RAYS != RAYS_DENSITY && mine) encode_ray_dir<NET>(M, lm, lane, d);
+    if (!rays_density_like(RAYS) && mine) encode_ray_dir<NET>(M, lm, lane, d);
     wave_sync();
     bool given = false;
     const HelpArgs ha = {hl, lm.W - wave, view};
@@ -1793,7 +1810,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
     const bool store = mine && !given;
     if (store) {  // get_image_and_depth, as in the tile loop
       float dn;  // (a helped ray is one of the caller's list: it was alive)
-      const float4 c = finish_pixel<RAYS != RAYS_NONE>(P, acc, near, far, view, RAYS != RAYS_NONE ? ray_number(P, pix_idx) : 0u, true, dn);
+      const float4 c = finish_pixel<RAYS != RAYS_NONE, RAYS == RAYS_HIT>(P, acc, near, far, view, RAYS != RAYS_NONE ? ray_number(P, pix_idx) : 0u, true, dn);
       store_ray_pixel<OUT8>(P, op.rgba, op.depth, pix_idx, c, dn);
     }
     if constexpr (U8) {  // (8-bit planes are row-major: the strip row of the rays' tile follows from a pixel index)
@@ -1878,6 +1895,7 @@ hipError_t launch_persistent_generic(const PersistLaunch& L);
 hipError_t launch_persistent_grid(const PersistLaunch& L);
 hipError_t launch_persistent_rays(const PersistLaunch& L);  // FrameParams::rays_o != nullptr, NET_HOT (nrf_kernels_rays.hip)
 hipError_t launch_persistent_rays_density(const PersistLaunch& L);  // its RAY_FLAG_DENSITY_ONLY twins, float planes (nrf_kernels_rays_density.hip)
+hipError_t launch_persistent_rays_hit(const PersistLaunch& L);  // its RAY_FLAG_HIT twins, float planes (nrf_kernels_rays_hit.hip)
 struct StripLaunch {
   const DevModel* M;
   const FrameParams* P;
@@ -1891,6 +1909,7 @@ struct StripLaunch {
 hipError_t launch_strip(const StripLaunch& L);
 hipError_t launch_strip_rays(const StripLaunch& L);  // FrameParams::rays_o != nullptr (nrf_kernels_rays.hip)
 hipError_t launch_strip_rays_density(const StripLaunch& L);  // its RAY_FLAG_DENSITY_ONLY twins (nrf_kernels_rays_density.hip)
+hipError_t launch_strip_rays_hit(const StripLaunch& L);  // its RAY_FLAG_HIT twins (nrf_kernels_rays_hit.hip)
 void preload_hot();
 void preload_hot_qqfh();
 void preload_hot_qqhh();
@@ -1902,6 +1921,7 @@ void preload_strip();
 void preload_grid();
 void preload_rays();
 void preload_rays_density();
+void preload_rays_hit();
 
 // one instance of the persistent form: WV waves per workgroup, WL = generic weights in LDS, 8-bit output / fast_interp chosen at run time
 // (GP: the gather plan, nrf_launch.h)

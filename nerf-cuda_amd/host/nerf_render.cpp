@@ -561,6 +561,26 @@ Image NerfRender::render_rays(const void* rays_o, const void* rays_d, uint64_t r
   return Image(resolution[0], resolution[1], m_rays_rgb.data(), m_rays_depth.data());
 }
 
+std::vector<float> NerfRender::ray_hits(const void* rays_o, const void* rays_d, uint64_t n, float opacity, const void* t_min, const void* t_max) {
+  if (!m_have_network) throw std::runtime_error{"ray_hits: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"ray_hits: single-device renderers only (device groups do not take rays)"};
+  const size_t px = (size_t)resolution[0] * resolution[1];
+  if (n < 1 || n > px) throw std::runtime_error{"ray_hits: 1 .. width * height rays (a list of n rays is a W x ceil(n / W) frame)"};
+  nrf_rays r{};
+  r.rays_o = rays_o;
+  r.rays_d = rays_d;
+  r.rays_per_view = n;
+  r.t_min = t_min;
+  r.t_max = t_max;
+  check(nrf_ray_hits(m_ctx[0], 1, &r, opacity, nullptr, nullptr), "nrf_ray_hits");
+  std::vector<float> rgba(4 * px), depth(px);
+  check(nrf_read_f32(m_ctx[0], rgba.data(), depth.data()), "nrf_read_f32");
+  std::vector<float> out(5 * (size_t)n);  // the records of the n rays, then their depths (row-major pixels: ray i is pixel i)
+  std::copy(rgba.begin(), rgba.begin() + 4 * (size_t)n, out.begin());
+  std::copy(depth.begin(), depth.begin() + (size_t)n, out.begin() + 4 * (size_t)n);
+  return out;
+}
+
 void NerfRender::generate_density_grid() {
   // reference nerf_render.cu:388-429 (dead there: the density query is commented out at :415); completed behind
   // nrf_generate_density_grid with the reference's constants: decay 0.95 (:392), start value 1/64 (:393), scale

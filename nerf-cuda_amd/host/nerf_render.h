@@ -86,6 +86,13 @@ class NerfRender {
   // So is the density-only mode for shadow and occlusion rays (NRF_RAYS_DENSITY_ONLY): it renders float planes only.
   Image render_rays(const void* rays_o, const void* rays_d, uint64_t rays_per_view, const void* t_min, const void* t_max,
                     const void* background);
+  // nrf_ray_hits (nerfhip.h): where each of n rays (device fp32 [n][3] origins and directions, n <= width * height of set_resolution;
+  // optional device fp32 [n] limits of t) first reaches the weight sum `opacity` -- picking, collision, the origins of shadow rays.
+  // Returns [n][4] records followed by [n] depths as host floats: a hit is (t of the crossing sample, its dt, the weight sum before it,
+  // the weight sum after it >= opacity), a miss (0, 0, 0, the final weight sum < opacity); the depth is the sum of w * t as composited.
+  // Single device only, as render_rays.
+  std::vector<float> ray_hits(const void* rays_o, const void* rays_d, uint64_t n, float opacity, const void* t_min = nullptr,
+                              const void* t_max = nullptr);
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in
   // nrf_generate_density_grid); reload_network_from_file calls it for a snapshot that carries no density grid
   void generate_density_grid();

@@ -192,6 +192,7 @@ _SIGS = {
                                    C.POINTER(Frame)]),
     "nrf_render_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Frame)]),
     "nrf_render_rays_clipped": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Rays), C.c_void_p, C.POINTER(Frame)]),
+    "nrf_ray_hits": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Rays), C.c_float, C.c_void_p, C.POINTER(Frame)]),
     "nrf_read_view_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nrf_read_view_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nrf_bind_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -673,6 +674,18 @@ class NerfHip:
                  background_ptr or None, int(flags), 0)
         f = Frame()
         _check(self.lib.nrf_render_rays_clipped(self.h, int(n_views), C.byref(r), C.c_void_p(stream or 0), C.byref(f)))
+        return f
+
+    def ray_hits(self, rays_o_ptr, rays_d_ptr, rays_per_view: int, opacity: float, t_min_ptr=0, t_max_ptr=0, n_views: int = 1,
+                 stream=None) -> Frame:
+        """nrf_ray_hits: where each ray's weight sum first reaches `opacity` (0 < opacity <= 1) -- the rays, t_min and t_max as in
+        render_rays_clipped, processed as its NRF_RAYS_DENSITY_ONLY mode processes them, and stopped at the first sample whose updated
+        weight sum is >= opacity.  rgba of a hit: (t of that sample as composited, its dt, the weight sum before it, the weight sum
+        after it); of a miss: (0, 0, 0, the final weight sum < opacity); without a ray: zeros.  depth: the sum of w * t as composited
+        (NRF_RAYS_DEPTH_T semantics).  Float outputs only; no background takes part."""
+        r = Rays(rays_o_ptr or None, rays_d_ptr or None, int(rays_per_view), t_min_ptr or None, t_max_ptr or None, None, 0, 0)
+        f = Frame()
+        _check(self.lib.nrf_ray_hits(self.h, int(n_views), C.byref(r), C.c_float(opacity), C.c_void_p(stream or 0), C.byref(f)))
         return f
 
     def read_view_f32(self, view: int):
