@@ -527,6 +527,35 @@ int nrf_mlp_forward_repeat(nrf_context* ctx, const void* feat_f16, const void* d
  * decompose (render_utils.h:308-334): -> sigma f32 [n], rgb f32 [n][3]       */
 int nrf_network(nrf_context* ctx, const void* xyz, const void* dir, uint32_t n,
                 void* sigma_f32, void* rgb_f32, void* stream);
+/* (ABI 7, additions) Density and its gradient at points and at ray hits: what a renderer with geometry of its own needs to light a
+ * hit of nrf_ray_hits, to offset its shadow ray and to respond to a collision -- which way the surface faces there.
+ * xyz: device fp32 [n][3] in the space nrf_network takes (nrf_march's output; o + t d of the rays of nrf_generate_rays /
+ * nrf_render_rays).  sigma is nrf_network's sigma bit for bit, from the density network alone: no directions, density_scale is
+ * not applied, options play no part.  The surface normal is -g / |g|; the kernel does not normalise (no sqrt, no division).
+ * Every operation below is ONE fp32 rounding (no contraction), so a host can replay it:
+ *   taps      for axis k:  xp = x_k + h,  xm = x_k - h;  a tap is the point with that one coordinate replaced.  Seven taps: the
+ *             centre, then +x, -x, +y, -y, +z, -z.
+ *   gradient  g_k = (s(xp) - s(xm)) * inv2h,  inv2h = 1.0f / (h + h) computed once on the host.
+ *   guard     a point is evaluated if and only if every coordinate of every tap is finite and within [-bound, bound]
+ *             (nrf_model_desc.bound); otherwise ALL its outputs are 0 and none of its taps is gathered.  nrf_density has the centre
+ *             tap only: |x_k| <= bound.  Exact: no clamping, no one-sided stencil.
+ * nrf_density:           sigma_f32 = device float [n].
+ * nrf_density_gradient:  out_f32x4 = device float4 [n] = (g_x, g_y, g_z, sigma at the point).
+ * nrf_hit_gradients:     the same at the hits of an nrf_ray_hits frame, without a round trip through the caller.  Pixel p of view v
+ *   of hits->rgba is a record (t, dt, ws0, ws1) and belongs to ray v * rays_per_view + p.  It is a hit if p < rays_per_view &&
+ *   ws1 >= opacity (the fp32 compare of nrf_ray_hits).  For a hit:  tq = t - frac * dt,  x_k = o_k + tq * d_k;  pos = (x, y, z, tq),
+ *   out = the gradient record at x under the same guard.  Every other pixel is zeros in both planes.  frac in [0, 1]: 1 is the start
+ *   of the crossing sample's interval, 0 its end, 0.5 the middle (for the refined t* of nrf_ray_hits compute positions yourself and
+ *   call nrf_density_gradient).  pos_f32x4 and out_f32x4 hold hits->n_views * hits->view_stride_px float4 each, in the frame's own
+ *   pixel order.  Of `rays` only rays_o, rays_d and rays_per_view (1 .. view_stride_px) are read.
+ * NRF_E_INVALID: a NULL pointer with n > 0; h not finite, <= 0 or > bound; frac outside [0, 1] or NaN; opacity outside (0, 1];
+ * hits->rgba == NULL.  NRF_E_UNSUPPORTED: a tile-major hit frame (shards, nrf_options.tile_major).  NRF_E_STATE: no model loaded.
+ * n == 0: NRF_OK, nothing done.  Stream and synchronisation rules are nrf_network's; the calls take no slot of the 16 calls in
+ * flight, leave nrf_get_stats untouched and write none of the context's frame buffers. */
+int nrf_density(nrf_context* ctx, const void* xyz, uint32_t n, void* sigma_f32, void* stream);
+int nrf_density_gradient(nrf_context* ctx, const void* xyz, uint32_t n, float h, void* out_f32x4, void* stream);
+int nrf_hit_gradients(nrf_context* ctx, const nrf_frame* hits, const nrf_rays* rays, float opacity, float frac, float h,
+                      void* pos_f32x4, void* out_f32x4, void* stream);
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

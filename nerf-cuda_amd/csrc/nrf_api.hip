@@ -24,6 +24,7 @@
 #include "nrf_grid_plan.h"
 #include "nrf_launch.h"
 #include "nrf_model_plan.h"
+#include "nrf_points_plan.h"
 
 using namespace nrf;
 
@@ -1707,6 +1708,66 @@ int nrf_network(nrf_context* c, const void* xyz, const void* dir, uint32_t n, vo
   STAGE_PROLOGUE();
   if (n && (!xyz || !dir || !sigma || !rgb)) return fail(NRF_E_INVALID, "null argument");
   HIP_TRY(launch_network(c->dm, xyz, dir, n, sigma, rgb, st));
+  STAGE_EPILOGUE();
+}
+
+// Point queries (nrf_kernels_points.hip; the arithmetic is nrf_points_plan.h): the stream rules of nrf_network, no slot of the
+// 16-call ring, no statistics, nothing of the context's frame buffers is written.
+int nrf_density(nrf_context* c, const void* xyz, uint32_t n, void* sigma, void* stream) {
+  STAGE_PROLOGUE();
+  if (n && (!xyz || !sigma)) return fail(NRF_E_INVALID, "null argument");
+  PointsArgs A;
+  A.xyz = (const float*)xyz;
+  A.n = n;
+  A.bound = c->desc.bound;
+  A.sigma = (float*)sigma;
+  HIP_TRY(launch_points(c->dm, POINTS_VALUE, A, st));
+  STAGE_EPILOGUE();
+}
+
+int nrf_density_gradient(nrf_context* c, const void* xyz, uint32_t n, float h, void* out, void* stream) {
+  STAGE_PROLOGUE();
+  if (n && (!xyz || !out)) return fail(NRF_E_INVALID, "null argument");
+  if (!points_step_valid(h, c->desc.bound)) return fail(NRF_E_INVALID, "nrf_density_gradient: h must be finite, > 0 and <= bound");
+  PointsArgs A;
+  A.xyz = (const float*)xyz;
+  A.n = n;
+  A.bound = c->desc.bound;
+  A.h = h;
+  A.inv2h = points_inv2h(h);
+  A.out = (float*)out;
+  HIP_TRY(launch_points(c->dm, POINTS_GRADIENT, A, st));
+  STAGE_EPILOGUE();
+}
+
+int nrf_hit_gradients(nrf_context* c, const nrf_frame* hits, const nrf_rays* rays, float opacity, float frac, float h, void* pos,
+                      void* out, void* stream) {
+  STAGE_PROLOGUE();
+  if (!hits || !rays || !rays->rays_o || !rays->rays_d || !pos || !out) return fail(NRF_E_INVALID, "null argument");
+  if (!hits->rgba) return fail(NRF_E_INVALID, "nrf_hit_gradients: the hit frame has no rgba plane");
+  if (!points_step_valid(h, c->desc.bound)) return fail(NRF_E_INVALID, "nrf_hit_gradients: h must be finite, > 0 and <= bound");
+  if (!points_frac_valid(frac)) return fail(NRF_E_INVALID, "nrf_hit_gradients: frac must be in [0, 1]");  // (NaN fails both)
+  if (!points_opacity_valid(opacity)) return fail(NRF_E_INVALID, "nrf_hit_gradients: opacity must be in (0, 1]");
+  if (hits->tile_major) return fail(NRF_E_UNSUPPORTED, "nrf_hit_gradients needs a row-major hit frame (one shard, tile_major 0)");
+  if (hits->n_views < 1 || hits->view_stride_px < 1 || (uint64_t)hits->n_views * (uint64_t)hits->view_stride_px > 0xffffffffull)
+    return fail(NRF_E_INVALID, "nrf_hit_gradients: the hit frame's n_views * view_stride_px must be 1 .. 2^32 - 1");
+  if (rays->rays_per_view < 1 || rays->rays_per_view > (uint64_t)hits->view_stride_px)
+    return fail(NRF_E_INVALID, "nrf_hit_gradients: rays_per_view must be 1 .. the hit frame's view_stride_px");
+  PointsArgs A;
+  A.hits = (const float*)hits->rgba;
+  A.rays_o = (const float*)rays->rays_o;
+  A.rays_d = (const float*)rays->rays_d;
+  A.n = (uint32_t)((uint64_t)hits->n_views * (uint64_t)hits->view_stride_px);
+  A.stride_px = (uint32_t)hits->view_stride_px;
+  A.per_view = (uint32_t)rays->rays_per_view;
+  A.bound = c->desc.bound;
+  A.h = h;
+  A.inv2h = points_inv2h(h);
+  A.opacity = opacity;
+  A.frac = frac;
+  A.out = (float*)out;
+  A.pos = (float*)pos;
+  HIP_TRY(launch_points(c->dm, POINTS_HIT_GRADIENT, A, st));
   STAGE_EPILOGUE();
 }
 

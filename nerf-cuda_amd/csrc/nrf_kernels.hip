@@ -323,7 +323,8 @@ __global__ __launch_bounds__(256) void gen_mlp_forward_kernel(const DevModel M, 
 }
 
 // Whole network on raw march output through the SAME code path as render_kernel.
-// DENSITY_ONLY (generic or hot): sigma only, rgb untouched (density-grid generation evaluates positions without directions).
+// (Both networks, always: sigma of the density network alone, at positions without directions, is points_kernel's --
+// nrf_kernels_points.hip, nrf_density.)
 template <int NET>
 __global__ __launch_bounds__(256, 2) void network_kernel(const DevModel M, const float* __restrict__ xyz,
                                                       const float* __restrict__ dir, uint32_t n, float* __restrict__ sigma,

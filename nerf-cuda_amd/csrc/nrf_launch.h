@@ -72,6 +72,22 @@ hipError_t launch_encode_dir(const DevModel& M, const void* dir01, uint32_t n, v
 hipError_t launch_mlp_forward(const DevModel& M, const void* feat, const void* dirfeat, uint32_t n, void* out, uint32_t repeat,
                               hipStream_t st);
 hipError_t launch_network(const DevModel& M, const void* xyz, const void* dir, uint32_t n, void* sigma, void* rgb, hipStream_t st);
+// Point queries (nrf_kernels_points.hip, arithmetic: nrf_points_plan.h): sigma of the density network alone at points
+// (POINTS_VALUE), its central differences (POINTS_GRADIENT), the same at the hits of an nrf_ray_hits frame (POINTS_HIT_GRADIENT).
+// Launch sizes and LDS are launch_network's for the model's stage instance.
+struct PointsArgs {
+  const float* xyz = nullptr;     // VALUE / GRADIENT: [n][3]
+  const float* hits = nullptr;    // HIT_GRADIENT: the frame's records [n][4], n = n_views * stride_px pixels
+  const float* rays_o = nullptr;  // HIT_GRADIENT: [n_views][per_view][3]
+  const float* rays_d = nullptr;
+  uint32_t n = 0;
+  uint32_t stride_px = 1, per_view = 0;  // HIT_GRADIENT: pixel i is pixel i % stride_px of view i / stride_px; it has a ray if that is < per_view
+  float bound = 0.f, h = 0.f, inv2h = 0.f, opacity = 0.f, frac = 0.f;
+  float* sigma = nullptr;  // VALUE: [n]
+  float* out = nullptr;    // GRADIENT / HIT_GRADIENT: [n][4] = (g_x, g_y, g_z, sigma)
+  float* pos = nullptr;    // HIT_GRADIENT: [n][4] = (x, y, z, tq)
+};
+hipError_t launch_points(const DevModel& M, int mode, const PointsArgs& A, hipStream_t st);
 hipError_t launch_density_positions(uint32_t H, float k, void* xyz, void* dir, hipStream_t st);
 hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int n_iterations, void* grid, hipStream_t st);
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,

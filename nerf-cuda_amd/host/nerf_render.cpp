@@ -581,6 +581,49 @@ std::vector<float> NerfRender::ray_hits(const void* rays_o, const void* rays_d, 
   return out;
 }
 
+void NerfRender::density(const void* xyz, uint32_t n, void* sigma_dev) {
+  if (!m_have_network) throw std::runtime_error{"density: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"density: single-device renderers only"};
+  check(nrf_density(m_ctx[0], xyz, n, sigma_dev, nullptr), "nrf_density");
+}
+
+void NerfRender::density_gradient(const void* xyz, uint32_t n, float h, void* out_dev) {
+  if (!m_have_network) throw std::runtime_error{"density_gradient: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"density_gradient: single-device renderers only"};
+  check(nrf_density_gradient(m_ctx[0], xyz, n, h, out_dev, nullptr), "nrf_density_gradient");
+}
+
+void NerfRender::hit_gradients(const void* rays_o, const void* rays_d, uint64_t n, float opacity, float frac, float h, void* pos_dev,
+                               void* out_dev, const void* t_min, const void* t_max) {
+  if (!m_have_network) throw std::runtime_error{"hit_gradients: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"hit_gradients: single-device renderers only (device groups do not take rays)"};
+  const size_t px = (size_t)resolution[0] * resolution[1];
+  if (n < 1 || n > px) throw std::runtime_error{"hit_gradients: 1 .. width * height rays (a list of n rays is a W x ceil(n / W) frame)"};
+  nrf_rays r{};
+  r.rays_o = rays_o;
+  r.rays_d = rays_d;
+  r.rays_per_view = n;
+  r.t_min = t_min;
+  r.t_max = t_max;
+  nrf_frame hits{};
+  check(nrf_ray_hits(m_ctx[0], 1, &r, opacity, nullptr, &hits), "nrf_ray_hits");
+  check(nrf_hit_gradients(m_ctx[0], &hits, &r, opacity, frac, h, pos_dev, out_dev, nullptr), "nrf_hit_gradients");
+}
+
+std::vector<float> NerfRender::normals_from_gradients(const std::vector<float>& records) {
+  const size_t m = records.size() / 4;
+  std::vector<float> normals(3 * m, 0.0f);
+  for (size_t i = 0; i < m; ++i) {
+    const double gx = records[4 * i], gy = records[4 * i + 1], gz = records[4 * i + 2];
+    const double len = std::sqrt(gx * gx + gy * gy + gz * gz);
+    if (!(len > 0.0)) continue;
+    normals[3 * i] = (float)(-gx / len);
+    normals[3 * i + 1] = (float)(-gy / len);
+    normals[3 * i + 2] = (float)(-gz / len);
+  }
+  return normals;
+}
+
 void NerfRender::generate_density_grid() {
   // reference nerf_render.cu:388-429 (dead there: the density query is commented out at :415); completed behind
   // nrf_generate_density_grid with the reference's constants: decay 0.95 (:392), start value 1/64 (:393), scale

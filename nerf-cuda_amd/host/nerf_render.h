@@ -93,6 +93,18 @@ class NerfRender {
   // Single device only, as render_rays.
   std::vector<float> ray_hits(const void* rays_o, const void* rays_d, uint64_t n, float opacity, const void* t_min = nullptr,
                               const void* t_max = nullptr);
+  // nrf_density / nrf_density_gradient (nerfhip.h): sigma of the density network alone at n points (device fp32 [n][3]) into device
+  // float [n], and (g_x, g_y, g_z, sigma) by central differences of step h into device float4 [n].  A point with a tap coordinate
+  // that is not finite or outside [-bound, bound] yields zeros.  Synchronous; single device only, as render_rays.
+  void density(const void* xyz, uint32_t n, void* sigma_dev);
+  void density_gradient(const void* xyz, uint32_t n, float h, void* out_dev);
+  // nrf_ray_hits followed by nrf_hit_gradients on its frame: for each of the n rays that reaches `opacity`, pos (device float4
+  // [width * height]) = (x, y, z, tq) with tq = t - frac * dt on the ray and out (likewise) = the gradient record there; zeros for
+  // every other pixel.  The records themselves stay readable as after ray_hits (nrf_read_f32).
+  void hit_gradients(const void* rays_o, const void* rays_d, uint64_t n, float opacity, float frac, float h, void* pos_dev, void* out_dev,
+                     const void* t_min = nullptr, const void* t_max = nullptr);
+  // surface normals of host copies of such records ([m][4]): -g / |g|, zero where |g| == 0 -> [m][3]
+  static std::vector<float> normals_from_gradients(const std::vector<float>& records);
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in
   // nrf_generate_density_grid); reload_network_from_file calls it for a snapshot that carries no density grid
   void generate_density_grid();

@@ -255,6 +255,10 @@ _SIGS = {
     "nrf_mlp_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nrf_mlp_forward_repeat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nrf_network": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_density": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "nrf_density_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+    "nrf_hit_gradients": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Rays), C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -794,6 +798,26 @@ class NerfHip:
         _check(self.lib.nrf_network(self.h, C.c_void_p(xyz), C.c_void_p(dirs), n, C.c_void_p(sigma), C.c_void_p(rgb),
                                     C.c_void_p(stream or 0)))
 
+    def density(self, xyz, n, sigma, stream=None):
+        """nrf_density: sigma of the density network alone at n points (device fp32 [n][3] -> [n]) -- nrf_network's sigma bit for
+        bit; a point with a coordinate that is not finite or outside [-bound, bound] yields 0."""
+        _check(self.lib.nrf_density(self.h, C.c_void_p(xyz), int(n), C.c_void_p(sigma), C.c_void_p(stream or 0)))
+
+    def density_gradient(self, xyz, n, h, out, stream=None):
+        """nrf_density_gradient: out (device float4 [n]) = (g_x, g_y, g_z, sigma), g_k = (sigma(x + h e_k) - sigma(x - h e_k)) *
+        fp32(1 / (h + h)); a point with any tap coordinate not finite or outside [-bound, bound] yields zeros.  The surface normal
+        is normals_from_gradients(out)."""
+        _check(self.lib.nrf_density_gradient(self.h, C.c_void_p(xyz), int(n), C.c_float(h), C.c_void_p(out), C.c_void_p(stream or 0)))
+
+    def hit_gradients(self, hits: Frame, rays_o_ptr, rays_d_ptr, rays_per_view: int, opacity: float, frac: float, h: float, pos, out,
+                      stream=None):
+        """nrf_hit_gradients: the gradient records at the hits of the nrf_ray_hits frame `hits` (row-major), for the rays it was
+        made from.  pos, out: device float4 [hits.n_views * hits.view_stride_px]; a hit pixel gets pos = (x, y, z, tq) with
+        tq = t - frac * dt, x = o + tq d, and out = the record of density_gradient at x; every other pixel zeros."""
+        r = Rays(rays_o_ptr or None, rays_d_ptr or None, int(rays_per_view), None, None, None, 0, 0)
+        _check(self.lib.nrf_hit_gradients(self.h, C.byref(hits), C.byref(r), C.c_float(opacity), C.c_float(frac), C.c_float(h),
+                                          C.c_void_p(pos), C.c_void_p(out), C.c_void_p(stream or 0)))
+
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
         pose = np.ascontiguousarray(pose, dtype=np.float32).reshape(16)
@@ -808,6 +832,14 @@ class NerfHip:
     def composite(self, sigmas, rgbs, deltas, n, n_step, rays_t, state, stream=None):
         _check(self.lib.nrf_composite(self.h, C.c_void_p(sigmas), C.c_void_p(rgbs), C.c_void_p(deltas), n, n_step,
                                       C.c_void_p(rays_t), C.c_void_p(state), C.c_void_p(stream or 0)))
+
+
+def normals_from_gradients(out):
+    """Surface normals of gradient records (nrf_density_gradient / nrf_hit_gradients: [..., 4] = g_x, g_y, g_z, sigma): -g / |g|,
+    and zero where |g| == 0 (a refused point, a miss, a flat spot)."""
+    g = np.asarray(out, np.float32)[..., :3]
+    norm = np.sqrt(np.sum(g.astype(np.float64) ** 2, axis=-1, keepdims=True))
+    return np.where(norm > 0, -g / np.where(norm > 0, norm, 1.0), 0.0).astype(np.float32)
 
 
 CS_LINEAR, CS_SRGB, CS_VISPOSNEG = 0, 1, 2
