@@ -556,6 +556,53 @@ int nrf_density(nrf_context* ctx, const void* xyz, uint32_t n, void* sigma_f32, 
 int nrf_density_gradient(nrf_context* ctx, const void* xyz, uint32_t n, float h, void* out_f32x4, void* stream);
 int nrf_hit_gradients(nrf_context* ctx, const nrf_frame* hits, const nrf_rays* rays, float opacity, float frac, float h,
                       void* pos_f32x4, void* out_f32x4, void* stream);
+/* (ABI 7, addition) Mesh extraction: the object itself -- a collision proxy, a shadow caster for a rasteriser, a preview or export
+ * mesh -- instead of answers per ray or per point.  The density network is evaluated on a lattice whose positions the kernel makes
+ * itself (no position upload), and the iso-surface is polygonised on the device by marching tetrahedra on the Kuhn split of each
+ * cell (six tetrahedra around the main diagonal): no ambiguous faces, so where the surface does not reach the lattice's boundary it is
+ * a closed, consistently oriented 2-manifold.  Every fp32 operation below is ONE rounding (no contraction), so a host can replay it:
+ *   lattice    dims = (nx, ny, nz), each >= 2; point (i, j, k) has the linear index p = (i * ny + j) * nz + k (z innermost) and the
+ *              position x_c = origin_c + (float)index_c * cell_c (the product is rounded, then the sum).
+ *   inside     sigma[p] >= iso (fp32 compare; NaN is outside).
+ *   vertices   point p owns edge m = 1 .. 7 to q = (i + (m & 1), j + ((m >> 1) & 1), k + ((m >> 2) & 1)) where q is in the lattice.
+ *              The edge crosses iff inside(p) != inside(q) and then carries one vertex: d = s_q - s_p, u = (iso - s_p) / d,
+ *              u = 0.5 unless 0 <= u <= 1 (infinite sigmas, NaN), v_c = x_p,c + u * (x_q,c - x_p,c).  Vertices are numbered in order
+ *              of p, then m.
+ *   triangles  the cell with min corner p (i < nx - 1, j < ny - 1, k < nz - 1) has the tetrahedra c0 = p, c1 = c0 + e_a, c2 = c1 + e_b,
+ *              c3 = p + (1, 1, 1) for (a, b, c) = xyz, xzy, yxz, yzx, zxy, zyx.  One corner L unlike the others r0 < r1 < r2: the
+ *              triangle (L-r0, L-r1, L-r2); two inside A < B, two outside C < D: (AC, AD, BD) and (AC, BD, BC); the last two indices
+ *              swapped where needed so that (b - a) x (c - a) points from inside to outside (counter-clockwise seen from outside).
+ *              Triangles are numbered in order of p, then tetrahedron, then as listed.  (csrc/nrf_mesh_plan.h is this text as code.)
+ * nrf_density_lattice: sigma_f32 = device float [nx][ny][nz], bit-identical to nrf_density on those positions: 0 where a coordinate is
+ *   outside [-bound, bound] (a lattice may stick out of the box).  Stream and synchronisation rules are nrf_density's.
+ * nrf_extract_mesh: sigma_f32 == NULL evaluates the lattice into a buffer of the context; otherwise it polygonises the caller's device
+ *   array float [nx][ny][nz] and needs no model.  The work is enqueued on `stream` (NULL: the context's) and the call returns after
+ *   it has completed: the sizes have to reach the host.  out->vertices (device float [n_vertices][3]) and out->triangles (device
+ *   uint32 [n_triangles][3]) are owned by the context, grow as needed and stay valid until the next nrf_extract_mesh or nrf_destroy;
+ *   out->sigma is the lattice that was used (the caller's pointer, or the context's buffer).  An empty surface is NRF_OK with zero
+ *   counts.  The vertex layout is [n][3] on purpose: nrf_density_gradient takes out->vertices as it is (n = n_vertices), and
+ *   -g / |g| of its records is the vertex normal.
+ * nrf_read_mesh: host copies of the last mesh (float [n_vertices][3], uint32 [n_triangles][3]); either may be NULL.
+ * NRF_E_INVALID: a NULL lattice or out (nrf_density_lattice: sigma_f32); a dimension below 2; nx * ny * nz > 2^27; a cell that is not
+ * finite or <= 0; a non-finite origin; a non-finite iso; reserved != 0.  NRF_E_STATE: no model loaded and no sigma given
+ * (nrf_read_mesh: no mesh extracted yet).  NRF_E_HIP with a message: the sigmas changed between the count and the emit pass (every
+ * write is checked against the counted sizes).  A refused call writes nothing.  The calls take no slot of the 16 calls in flight, leave
+ * nrf_get_stats untouched and write none of the context's frame buffers. */
+typedef struct nrf_lattice {
+  float origin[3];  /* position of point (0, 0, 0)                           */
+  float cell[3];    /* spacing per axis, > 0                                 */
+  uint32_t dims[3]; /* points per axis, >= 2                                 */
+  uint32_t reserved; /* 0                                                    */
+} nrf_lattice;
+typedef struct nrf_mesh {
+  uint64_t n_vertices, n_triangles;
+  void* vertices;  /* device float [n_vertices][3]                           */
+  void* triangles; /* device uint32 [n_triangles][3]                         */
+  void* sigma;     /* device float [nx][ny][nz]                              */
+} nrf_mesh;
+int nrf_density_lattice(nrf_context* ctx, const nrf_lattice* lattice, void* sigma_f32, void* stream);
+int nrf_extract_mesh(nrf_context* ctx, const nrf_lattice* lattice, float iso, const void* sigma_f32, void* stream, nrf_mesh* out);
+int nrf_read_mesh(nrf_context* ctx, float* vertices, uint32_t* triangles);
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

@@ -153,6 +153,14 @@ struct nrf_context {
   int sample_cap = 2;      // per-round sample queue of a ray by its transmittance (FrameParams::sample_cap); NRF_SAMPLE_CAP=0 / 1: A/B runs
   bool rendered = false;
   hipStream_t last_stream = nullptr;
+  // nrf_extract_mesh: the last mesh and the polygoniser's workspace, grown as needed (capacities in bytes)
+  struct MeshBuffers {
+    void *sigma = nullptr, *codes = nullptr, *vbase = nullptr, *tbase = nullptr, *partials = nullptr, *vertices = nullptr, *triangles = nullptr;
+    size_t cap_sigma = 0, cap_codes = 0, cap_vbase = 0, cap_tbase = 0, cap_partials = 0, cap_vertices = 0, cap_triangles = 0;
+    uint32_t* totals = nullptr;  // device: n_vertices, n_triangles, the emit pass's flag, 0
+    uint64_t n_vertices = 0, n_triangles = 0;
+    bool have = false;
+  } mesh;
 };
 
 namespace {
@@ -209,6 +217,24 @@ void free_frame(nrf_context* c) {
   c->d_rgba = c->d_depth = c->d_rgb8 = c->d_depth8 = nullptr;
   c->n_out_px = 0;
   c->rendered = false;
+}
+
+void free_mesh(nrf_context* c) {
+  auto& m = c->mesh;
+  for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, (void*)m.totals})
+    if (q) (void)hipFree(q);
+  m = nrf_context::MeshBuffers{};
+}
+
+// a buffer of the mesh extraction holds at least `need` bytes afterwards (its contents are not kept)
+int grow_mesh_buffer(void** p, size_t& cap, uint64_t need) {
+  if (need <= cap) return NRF_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  cap = 0;
+  HIP_TRY(hipMalloc(p, (size_t)need));
+  cap = (size_t)need;
+  return NRF_OK;
 }
 
 // the shard layout (tile-major [n_tiles][64]) instead of the row-major frame: every multi-shard render, and a single shard on request
@@ -483,6 +509,7 @@ int nrf_destroy(nrf_context* c) {
   free_model(c);
   free_frame(c);
   free_host_slots(c);
+  free_mesh(c);
   for (auto& h : c->hs) {
     if (h.done) (void)hipEventDestroy(h.done);
     for (hipEvent_t g : h.grp) if (g) (void)hipEventDestroy(g);
@@ -1769,6 +1796,91 @@ int nrf_hit_gradients(nrf_context* c, const nrf_frame* hits, const nrf_rays* ray
   A.pos = (float*)pos;
   HIP_TRY(launch_points(c->dm, POINTS_HIT_GRADIENT, A, st));
   STAGE_EPILOGUE();
+}
+
+// Mesh extraction (nrf_kernels_points.hip: the lattice mode; nrf_kernels_mesh.hip: the polygoniser; the arithmetic and the refusals
+// are nrf_mesh_plan.h's).  Like the point queries: no slot of the 16-call ring, no statistics, no frame buffer.
+static const char* lattice_refusal(const nrf_lattice* l, MeshLattice& L) {
+  if (!l) return "null lattice";
+  if (l->reserved != 0) return "nrf_lattice: reserved must be 0";
+  if (!mesh_lattice_valid(l->origin, l->cell, l->dims))
+    return "nrf_lattice: every dimension >= 2, at most 2^27 points, finite cells > 0 and a finite origin";
+  for (int k = 0; k < 3; ++k) L.origin[k] = l->origin[k], L.cell[k] = l->cell[k], L.dims[k] = l->dims[k];
+  return nullptr;
+}
+
+static hipError_t launch_lattice_sigma(const nrf_context* c, const MeshLattice& L, float* sigma, hipStream_t st) {
+  return launch_points_lattice(c->dm, L, c->desc.bound, sigma, st);
+}
+
+int nrf_density_lattice(nrf_context* c, const nrf_lattice* lattice, void* sigma, void* stream) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  MeshLattice L;
+  if (const char* why = lattice_refusal(lattice, L)) return fail(NRF_E_INVALID, why);
+  if (!sigma) return fail(NRF_E_INVALID, "null argument");
+  STAGE_PROLOGUE();
+  HIP_TRY(launch_lattice_sigma(c, L, (float*)sigma, st));
+  STAGE_EPILOGUE();
+}
+
+int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, const void* sigma, void* stream, nrf_mesh* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  MeshLattice L;
+  if (const char* why = lattice_refusal(lattice, L)) return fail(NRF_E_INVALID, why);
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (!mesh_iso_valid(iso)) return fail(NRF_E_INVALID, "nrf_extract_mesh: iso must be finite");
+  if (!sigma && !c->model_loaded) return fail(NRF_E_STATE, "no model loaded and no sigma given");
+  int rc = set_device(c);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  auto& m = c->mesh;
+  m.have = false;
+  const uint64_t n = mesh_points(L);
+  if ((rc = grow_mesh_buffer(&m.codes, m.cap_codes, n * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.vbase, m.cap_vbase, n * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.tbase, m.cap_tbase, n * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.partials, m.cap_partials, (uint64_t)mesh_scan_tiles((uint32_t)n) * 8))) return rc;
+  if (!m.totals) HIP_TRY(hipMalloc((void**)&m.totals, 16));
+  const float* s = (const float*)sigma;
+  if (!s) {
+    if ((rc = grow_mesh_buffer(&m.sigma, m.cap_sigma, mesh_sigma_bytes(n)))) return rc;
+    HIP_TRY(launch_lattice_sigma(c, L, (float*)m.sigma, st));
+    s = (const float*)m.sigma;
+  }
+  // count and scan; the sizes reach the host; emit into buffers of exactly checked sizes; the flag reaches the host
+  uint32_t host[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemsetAsync(m.totals, 0, 16, st));
+  HIP_TRY(launch_mesh_count(L, s, iso, (uint32_t*)m.codes, (uint32_t*)m.vbase, (uint32_t*)m.tbase, m.partials, m.totals, st));
+  HIP_TRY(hipMemcpyAsync(host, m.totals, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t nv = host[0], nt = host[1];
+  if ((rc = grow_mesh_buffer(&m.vertices, m.cap_vertices, mesh_vertex_bytes(nv)))) return rc;
+  if ((rc = grow_mesh_buffer(&m.triangles, m.cap_triangles, mesh_triangle_bytes(nt)))) return rc;
+  HIP_TRY(launch_mesh_emit(L, s, iso, (const uint32_t*)m.codes, (const uint32_t*)m.vbase, (const uint32_t*)m.tbase, nv, nt, (float*)m.vertices,
+                           (uint32_t*)m.triangles, m.totals + 2, st));
+  HIP_TRY(hipMemcpyAsync(host, m.totals, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (host[2]) return fail(NRF_E_HIP, "nrf_extract_mesh: the count and the emit pass disagree (the sigmas changed during the call); writes were dropped");
+  m.n_vertices = nv;
+  m.n_triangles = nt;
+  m.have = true;
+  out->n_vertices = nv;
+  out->n_triangles = nt;
+  out->vertices = nv ? m.vertices : nullptr;
+  out->triangles = nt ? m.triangles : nullptr;
+  out->sigma = const_cast<float*>(s);
+  return NRF_OK;
+}
+
+int nrf_read_mesh(nrf_context* c, float* vertices, uint32_t* triangles) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!c->mesh.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const auto& m = c->mesh;
+  if (vertices && m.n_vertices) HIP_TRY(hipMemcpy(vertices, m.vertices, (size_t)mesh_vertex_bytes(m.n_vertices), hipMemcpyDeviceToHost));
+  if (triangles && m.n_triangles) HIP_TRY(hipMemcpy(triangles, m.triangles, (size_t)mesh_triangle_bytes(m.n_triangles), hipMemcpyDeviceToHost));
+  return NRF_OK;
 }
 
 int nrf_generate_rays(nrf_context* c, const float cam[4], const float pose[16], void* rays_o, void* rays_d, void* nears,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "nrf_grid_plan.h"  // persistent_lds_total: the sum plan_grid and launch_render share
+#include "nrf_mesh_plan.h"  // MeshLattice
 
 namespace nrf {
 // Instances of the render kernel (nrf_render.h), one id for host and device code.  DevModel::net renders the frames;
@@ -88,6 +89,20 @@ struct PointsArgs {
   float* pos = nullptr;    // HIT_GRADIENT: [n][4] = (x, y, z, tq)
 };
 hipError_t launch_points(const DevModel& M, int mode, const PointsArgs& A, hipStream_t st);
+// POINTS_VALUE at the mesh_points(L) points of a lattice (points_lattice_kernel): sigma [nx][ny][nz]; no position array is read
+hipError_t launch_points_lattice(const DevModel& M, const MeshLattice& L, float bound, float* sigma, hipStream_t st);
+// Mesh extraction (nrf_kernels_mesh.hip, arithmetic: nrf_mesh_plan.h) on a lattice of n = mesh_points(L) sigmas:
+//   launch_mesh_count  codes[n] (mesh_count_point), then vbase[n] / tbase[n] = the exclusive prefix sums of the codes' vertex and
+//                      triangle counts and totals[0 .. 1] = the sums; partials: mesh_scan_tiles(n) uint2 of workspace
+//   launch_mesh_emit   vertices [n_vertices][3] and triangles [n_triangles][3] at the scanned offsets; *flag is set to 1 when a write
+//                      was dropped because it would have fallen outside those counts
+constexpr uint32_t MESH_SCAN_TILE = 2048;  // lattice points per workgroup of the scan: 256 lanes x 8
+inline uint32_t mesh_scan_tiles(uint32_t n) { return (n + MESH_SCAN_TILE - 1) / MESH_SCAN_TILE; }
+hipError_t launch_mesh_count(const MeshLattice& L, const float* sigma, float iso, uint32_t* codes, uint32_t* vbase, uint32_t* tbase,
+                             void* partials, uint32_t* totals, hipStream_t st);
+hipError_t launch_mesh_emit(const MeshLattice& L, const float* sigma, float iso, const uint32_t* codes, const uint32_t* vbase,
+                            const uint32_t* tbase, uint32_t n_vertices, uint32_t n_triangles, float* vertices, uint32_t* triangles,
+                            uint32_t* flag, hipStream_t st);
 hipError_t launch_density_positions(uint32_t H, float k, void* xyz, void* dir, hipStream_t st);
 hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int n_iterations, void* grid, hipStream_t st);
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,

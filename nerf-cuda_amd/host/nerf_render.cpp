@@ -610,6 +610,40 @@ void NerfRender::hit_gradients(const void* rays_o, const void* rays_d, uint64_t 
   check(nrf_hit_gradients(m_ctx[0], &hits, &r, opacity, frac, h, pos_dev, out_dev, nullptr), "nrf_hit_gradients");
 }
 
+NerfRender::Mesh NerfRender::extract_mesh(const float origin[3], const float cell[3], const uint32_t dims[3], float iso) {
+  if (!m_have_network) throw std::runtime_error{"extract_mesh: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"extract_mesh: single-device renderers only"};
+  nrf_lattice l{};
+  for (int k = 0; k < 3; ++k) l.origin[k] = origin[k], l.cell[k] = cell[k], l.dims[k] = dims[k];
+  nrf_mesh m{};
+  check(nrf_extract_mesh(m_ctx[0], &l, iso, nullptr, nullptr, &m), "nrf_extract_mesh");
+  Mesh out;
+  out.vertices.resize(3 * (size_t)m.n_vertices);
+  out.triangles.resize(3 * (size_t)m.n_triangles);
+  check(nrf_read_mesh(m_ctx[0], out.vertices.data(), out.triangles.data()), "nrf_read_mesh");
+  out.vertices_dev = m.vertices;
+  return out;
+}
+
+bool NerfRender::save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
+                          const std::vector<float>& normals) {
+  std::FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return false;
+  const size_t nv = vertices.size() / 3, nt = triangles.size() / 3;
+  const bool with_normals = nv > 0 && normals.size() == 3 * nv;
+  std::fprintf(f, "# %zu vertices, %zu triangles\n", nv, nt);
+  for (size_t i = 0; i < nv; ++i) std::fprintf(f, "v %.9g %.9g %.9g\n", vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
+  if (with_normals)
+    for (size_t i = 0; i < nv; ++i) std::fprintf(f, "vn %.9g %.9g %.9g\n", normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+  for (size_t i = 0; i < nt; ++i) {
+    const unsigned long a = triangles[3 * i] + 1ul, b = triangles[3 * i + 1] + 1ul, c = triangles[3 * i + 2] + 1ul;
+    if (with_normals) std::fprintf(f, "f %lu//%lu %lu//%lu %lu//%lu\n", a, a, b, b, c, c);
+    else std::fprintf(f, "f %lu %lu %lu\n", a, b, c);
+  }
+  const bool ok = !std::ferror(f);
+  return std::fclose(f) == 0 && ok;
+}
+
 std::vector<float> NerfRender::normals_from_gradients(const std::vector<float>& records) {
   const size_t m = records.size() / 4;
   std::vector<float> normals(3 * m, 0.0f);

@@ -105,6 +105,20 @@ class NerfRender {
                      const void* t_min = nullptr, const void* t_max = nullptr);
   // surface normals of host copies of such records ([m][4]): -g / |g|, zero where |g| == 0 -> [m][3]
   static std::vector<float> normals_from_gradients(const std::vector<float>& records);
+  // nrf_extract_mesh (nerfhip.h): the iso-surface sigma == iso of the density network on the lattice of dims points per axis at
+  // origin + index * cell, by marching tetrahedra on the device -> host vertices [n][3] and triangles [m][3] (counter-clockwise seen
+  // from outside).  vertices_dev is the device copy ([n][3], owned by the context until the next extract_mesh): density_gradient
+  // takes it as it is, and normals_from_gradients of a host copy of its records are the vertex normals.  Synchronous; single device.
+  struct Mesh {
+    std::vector<float> vertices;
+    std::vector<uint32_t> triangles;
+    const void* vertices_dev = nullptr;
+  };
+  Mesh extract_mesh(const float origin[3], const float cell[3], const uint32_t dims[3], float iso);
+  // Wavefront OBJ: "v x y z" per vertex, "vn x y z" per vertex when normals ([n][3]) has one per vertex, faces 1-based ("f a//a b//b c//c"
+  // with normals, "f a b c" without).  Returns false when the file cannot be written.
+  static bool save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
+                       const std::vector<float>& normals = {});
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in
   // nrf_generate_density_grid); reload_network_from_file calls it for a snapshot that carries no density grid
   void generate_density_grid();

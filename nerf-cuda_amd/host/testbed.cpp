@@ -4,6 +4,8 @@
 //   usage: testbed [snapshot.msgpack] [width height] [out_prefix] [transforms.json]
 // With a transforms.json (NeRF-synthetic / instant-ngp camera path) every frame of the path is rendered as well, in
 // batches of 32 views per launch, and written to <out_prefix>path_NNNN.rgb.
+//   options (anywhere): --save_mesh FILE.obj [--mesh_res N] [--mesh_iso X] -- the iso-surface of the density on an N^3 lattice over the
+//   model's aabb (NerfRender::extract_mesh; defaults 128 and 2.5), written as a Wavefront OBJ
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -21,6 +23,24 @@ using namespace ngp;
 
 int main(int argc, char** argv) {
   std::cout << "Hello, Metavese!" << std::endl;
+  // the options, taken out of argv: what remains are the positional arguments above
+  std::string mesh_path;
+  int mesh_res = 128;
+  float mesh_iso = 2.5f;  // (instant-ngp's default mesh threshold)
+  {
+    int kept = 1;
+    for (int i = 1; i < argc; ++i) {
+      const std::string a = argv[i];
+      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso") && i + 1 < argc) {
+        if (a == "--save_mesh") mesh_path = argv[++i];
+        else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
+        else mesh_iso = (float)std::atof(argv[++i]);
+      } else {
+        argv[kept++] = argv[i];
+      }
+    }
+    argc = kept;
+  }
   try {
     NerfRender* render = new NerfRender();
     const std::string config_path = argc > 1 ? argv[1] : "freality.msgpack";
@@ -82,6 +102,29 @@ int main(int argc, char** argv) {
       }
       const auto p1 = std::chrono::steady_clock::now();
       std::printf("camera path: %zu frames, %f s / frame\n", done, std::chrono::duration<double>(p1 - p0).count() / (double)(done ? done : 1));
+    }
+    if (!mesh_path.empty()) {
+      // a cube of mesh_res^3 points over the model's aabb [-bound, bound]^3 (the density is 0 outside it, so the surface is closed
+      // wherever the object does not touch the box)
+      const float b = render->model_desc().bound;
+      const uint32_t n = (uint32_t)std::max(2, mesh_res);
+      const float origin[3] = {-b, -b, -b}, step = 2.0f * b / (float)(n - 1), cell[3] = {step, step, step};
+      const uint32_t dims[3] = {n, n, n};
+      const auto m0 = std::chrono::steady_clock::now();
+      const NerfRender::Mesh mesh = render->extract_mesh(origin, cell, dims, mesh_iso);
+      const auto m1 = std::chrono::steady_clock::now();
+      std::printf("mesh: %u^3 lattice at iso %g: %zu vertices, %zu triangles, %f s\n", n, mesh_iso, mesh.vertices.size() / 3,
+                  mesh.triangles.size() / 3, std::chrono::duration<double>(m1 - m0).count());
+      // vertex normals: nrf_density_gradient takes the device vertices as they are; its records need n float4 of device memory,
+      // which an n x 1 render buffer's accumulate plane is
+      std::vector<float> normals;
+      if (!mesh.vertices.empty()) {
+        RenderBuffer records;
+        records.resize(Vector2i((int)(mesh.vertices.size() / 3), 1));
+        render->density_gradient(mesh.vertices_dev, (uint32_t)(mesh.vertices.size() / 3), b / 128.0f, records.accumulate_buffer());
+        normals = NerfRender::normals_from_gradients(records.accumulate_buffer_host());
+      }
+      if (!NerfRender::save_obj(mesh_path, mesh.vertices, mesh.triangles, normals)) throw std::runtime_error{"cannot write " + mesh_path};
     }
     delete render;
   } catch (const std::exception& e) {

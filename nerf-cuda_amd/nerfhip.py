@@ -140,6 +140,36 @@ class Rays(C.Structure):
     ]
 
 
+class Lattice(C.Structure):
+    """nrf_lattice: point (i, j, k) of dims = (nx, ny, nz) lies at origin + (i, j, k) * cell and has the index (i * ny + j) * nz + k."""
+    _fields_ = [
+        ("origin", C.c_float * 3),
+        ("cell", C.c_float * 3),
+        ("dims", C.c_uint32 * 3),
+        ("reserved", C.c_uint32),
+    ]
+
+    @classmethod
+    def make(cls, origin, cell, dims):
+        return cls((C.c_float * 3)(*[float(v) for v in origin]), (C.c_float * 3)(*[float(v) for v in cell]),
+                   (C.c_uint32 * 3)(*[int(v) for v in dims]), 0)
+
+    @property
+    def n_points(self):
+        return int(self.dims[0]) * int(self.dims[1]) * int(self.dims[2])
+
+
+class Mesh(C.Structure):
+    """nrf_mesh: device pointers owned by the context, valid until the next extract_mesh or close."""
+    _fields_ = [
+        ("n_vertices", C.c_uint64),
+        ("n_triangles", C.c_uint64),
+        ("vertices", C.c_void_p),   # float [n_vertices][3]
+        ("triangles", C.c_void_p),  # uint32 [n_triangles][3]
+        ("sigma", C.c_void_p),      # float [nx][ny][nz]
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64),
@@ -259,6 +289,9 @@ _SIGS = {
     "nrf_density_gradient": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
     "nrf_hit_gradients": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.POINTER(Rays), C.c_float, C.c_float, C.c_float, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "nrf_density_lattice": (C.c_int, [C.c_void_p, C.POINTER(Lattice), C.c_void_p, C.c_void_p]),
+    "nrf_extract_mesh": (C.c_int, [C.c_void_p, C.POINTER(Lattice), C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Mesh)]),
+    "nrf_read_mesh": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -817,6 +850,29 @@ class NerfHip:
         r = Rays(rays_o_ptr or None, rays_d_ptr or None, int(rays_per_view), None, None, None, 0, 0)
         _check(self.lib.nrf_hit_gradients(self.h, C.byref(hits), C.byref(r), C.c_float(opacity), C.c_float(frac), C.c_float(h),
                                           C.c_void_p(pos), C.c_void_p(out), C.c_void_p(stream or 0)))
+
+    def density_lattice(self, lattice: Lattice, sigma, stream=None):
+        """nrf_density_lattice: sigma (device fp32 [nx][ny][nz]) at every point of the lattice, bit-identical to density() on the
+        positions origin + (float)index * cell; 0 where a coordinate is outside [-bound, bound].  No positions are uploaded."""
+        _check(self.lib.nrf_density_lattice(self.h, C.byref(lattice), C.c_void_p(sigma), C.c_void_p(stream or 0)))
+
+    def extract_mesh(self, lattice: Lattice, iso: float, sigma=None, stream=None) -> Mesh:
+        """nrf_extract_mesh: the iso-surface sigma == iso of the lattice by marching tetrahedra, on the device.  sigma None: the
+        model is evaluated on the lattice; otherwise the caller's device array [nx][ny][nz] is polygonised (no model needed).
+        Returns after completion.  mesh.vertices is [n][3]: density_gradient(mesh.vertices, mesh.n_vertices, h, out) takes it as it
+        is, and normals_from_gradients(out) are the vertex normals."""
+        out = Mesh()
+        _check(self.lib.nrf_extract_mesh(self.h, C.byref(lattice), C.c_float(iso), C.c_void_p(sigma or 0), C.c_void_p(stream or 0),
+                                         C.byref(out)))
+        self._mesh_counts = (int(out.n_vertices), int(out.n_triangles))
+        return out
+
+    def read_mesh(self):
+        """nrf_read_mesh: (vertices float32 [n_vertices][3], triangles uint32 [n_triangles][3]) of the last extract_mesh"""
+        nv, nt = getattr(self, "_mesh_counts", (0, 0))
+        v, t = np.empty((nv, 3), np.float32), np.empty((nt, 3), np.uint32)
+        _check(self.lib.nrf_read_mesh(self.h, v.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return v, t
 
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
