@@ -603,6 +603,49 @@ typedef struct nrf_mesh {
 int nrf_density_lattice(nrf_context* ctx, const nrf_lattice* lattice, void* sigma_f32, void* stream);
 int nrf_extract_mesh(nrf_context* ctx, const nrf_lattice* lattice, float iso, const void* sigma_f32, void* stream, nrf_mesh* out);
 int nrf_read_mesh(nrf_context* ctx, float* vertices, uint32_t* triangles);
+/* (ABI 7, addition) Unit normals and colours at points and at mesh vertices: what an exported mesh needs besides positions and
+ * triangles, and what a rasteriser needs to draw the proxy it has just extracted -- in one launch, without a round trip through the
+ * caller.  Seven network passes per point: the six off-centre taps of nrf_density_gradient through the density network alone, then the
+ * centre through both networks, looked at along a direction the kernel forms itself.  The gradient record (g_x, g_y, g_z) is
+ * nrf_density_gradient's, bit for bit: the same taps, the same guard, the same inv2h.  Every operation below is ONE fp32 rounding (no
+ * contraction), the square root and the division the correctly rounded IEEE ones, so a host can replay it:
+ *   l2   = (g_x * g_x + g_y * g_y) + g_z * g_z          three products, two sums, in this order
+ *   ok   = l2 is finite && l2 >= 2^-60                   (false for NaN; the floor makes the result independent of the denormal mode)
+ *   len  = ok ? sqrt(l2) : 0
+ *   d_k  = ok ? g_k / len : 0                            the direction of a viewer's ray that meets the surface head-on, from outside
+ *   n_k  = -d_k                                          exact: the outward normal -g / |g|.  A degenerate point (ok false) has
+ *                                                        n = d = (+0, +0, +0), not -0
+ *   direction  the network is given u_k = 0.5f * v_k (rounded), then + 0.5f (rounded), as nrf_network forms it, with v = d (dir == NULL)
+ *              or v = the caller's direction: not normalised, not checked.  A direction never becomes an address.
+ *   guard      nrf_density_gradient's: a point is evaluated if and only if every coordinate of every one of its seven taps is finite and
+ *              within [-bound, bound]; otherwise BOTH its records are zeros and none of its taps is gathered.
+ * nrf_point_attributes: xyz = device fp32 [n][3], as nrf_density_gradient takes it (nrf_mesh.vertices goes in as it is); dir = device
+ *   fp32 [n][3] or NULL.  normal_f32x4 = device float4 [n] = (n_x, n_y, n_z, sigma at the point); color_f32x4 = device float4 [n] =
+ *   (r, g, b, len).  sigma and rgb are those of nrf_network at (x, v), bit for bit.  With a given direction the six taps still run: the
+ *   normal is reported all the same.  A degenerate point has n = 0, len = 0 and, with dir == NULL, the direction (0, 0, 0); its sigma and
+ *   its colour are still evaluated: a flat region has a colour too.
+ * nrf_mesh_attributes: the same at the vertices of the context's last nrf_extract_mesh, with dir == NULL, into two buffers owned by the
+ *   context (device float4 [n_vertices] each): they grow as needed and stay valid until the next nrf_extract_mesh, nrf_mesh_attributes
+ *   or nrf_destroy.  The work is enqueued on `stream` (NULL: the context's) and the call returns after it has completed, as
+ *   nrf_extract_mesh does.  A vertex whose stencil leaves [-bound, bound] gets zeros in both records: on a lattice that spans the whole
+ *   box (testbed's) those are the vertices within h of a face.  An empty mesh is NRF_OK with n_vertices = 0.
+ * nrf_read_mesh_attributes: host copies of the last attributes (float [n_vertices][4] each); either may be NULL.
+ * An exported colour byte is the library's 8-bit rule of nrf_read_u8: (unsigned char)(255.0 * x), saturating, NaN -> 0.
+ * NRF_E_INVALID: a NULL xyz, normal or colour pointer with n > 0 (nrf_mesh_attributes: out); h not finite, <= 0 or > bound.  NRF_E_STATE:
+ * no model loaded (also for a mesh made from a caller's lattice on a context without a model: there is no network to ask); no mesh
+ * extracted yet; nrf_read_mesh_attributes: no attributes of the current mesh -- a new nrf_extract_mesh invalidates them.  n == 0: NRF_OK,
+ * nothing done.  Stream and synchronisation rules of nrf_point_attributes are nrf_network's.  A refused call writes nothing.  The calls
+ * take no slot of the 16 calls in flight, leave nrf_get_stats untouched and write none of the context's frame buffers.
+ * (csrc/nrf_attr_plan.h is this text as code.) */
+typedef struct nrf_mesh_attr {
+  uint64_t n_vertices;
+  void* normals; /* device float4 [n_vertices] = (n_x, n_y, n_z, sigma)      */
+  void* colors;  /* device float4 [n_vertices] = (r, g, b, len)              */
+} nrf_mesh_attr;
+int nrf_point_attributes(nrf_context* ctx, const void* xyz, const void* dir, uint32_t n, float h, void* normal_f32x4, void* color_f32x4,
+                         void* stream);
+int nrf_mesh_attributes(nrf_context* ctx, float h, void* stream, nrf_mesh_attr* out);
+int nrf_read_mesh_attributes(nrf_context* ctx, float* normals_f32x4, float* colors_f32x4);
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

@@ -160,6 +160,10 @@ struct nrf_context {
     uint32_t* totals = nullptr;  // device: n_vertices, n_triangles, the emit pass's flag, 0
     uint64_t n_vertices = 0, n_triangles = 0;
     bool have = false;
+    // nrf_mesh_attributes: float4 [n_vertices] each, of the mesh above (have_attr falls with every nrf_extract_mesh)
+    void *normals = nullptr, *colors = nullptr;
+    size_t cap_normals = 0, cap_colors = 0;
+    bool have_attr = false;
   } mesh;
 };
 
@@ -221,7 +225,7 @@ void free_frame(nrf_context* c) {
 
 void free_mesh(nrf_context* c) {
   auto& m = c->mesh;
-  for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, (void*)m.totals})
+  for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, m.normals, m.colors, (void*)m.totals})
     if (q) (void)hipFree(q);
   m = nrf_context::MeshBuffers{};
 }
@@ -1835,6 +1839,7 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   auto& m = c->mesh;
   m.have = false;
+  m.have_attr = false;
   const uint64_t n = mesh_points(L);
   if ((rc = grow_mesh_buffer(&m.codes, m.cap_codes, n * 4))) return rc;
   if ((rc = grow_mesh_buffer(&m.vbase, m.cap_vbase, n * 4))) return rc;
@@ -1880,6 +1885,63 @@ int nrf_read_mesh(nrf_context* c, float* vertices, uint32_t* triangles) {
   const auto& m = c->mesh;
   if (vertices && m.n_vertices) HIP_TRY(hipMemcpy(vertices, m.vertices, (size_t)mesh_vertex_bytes(m.n_vertices), hipMemcpyDeviceToHost));
   if (triangles && m.n_triangles) HIP_TRY(hipMemcpy(triangles, m.triangles, (size_t)mesh_triangle_bytes(m.n_triangles), hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// Point attributes (nrf_kernels_attr.hip; the arithmetic is nrf_attr_plan.h on top of nrf_points_plan.h): the stream rules of
+// nrf_network, no slot of the 16-call ring, no statistics, nothing of the context's frame buffers is written.
+static hipError_t launch_attributes(const nrf_context* c, const void* xyz, const void* dir, uint32_t n, float h, void* normal, void* color,
+                                    hipStream_t st) {
+  AttrArgs A;
+  A.xyz = (const float*)xyz;
+  A.dir = (const float*)dir;
+  A.n = n;
+  A.bound = c->desc.bound;
+  A.h = h;
+  A.inv2h = points_inv2h(h);
+  A.normal = (float*)normal;
+  A.color = (float*)color;
+  return launch_attr(c->dm, A, st);
+}
+
+int nrf_point_attributes(nrf_context* c, const void* xyz, const void* dir, uint32_t n, float h, void* normal, void* color, void* stream) {
+  STAGE_PROLOGUE();
+  if (n && (!xyz || !normal || !color)) return fail(NRF_E_INVALID, "null argument");
+  if (!points_step_valid(h, c->desc.bound)) return fail(NRF_E_INVALID, "nrf_point_attributes: h must be finite, > 0 and <= bound");
+  HIP_TRY(launch_attributes(c, xyz, dir, n, h, normal, color, st));
+  STAGE_EPILOGUE();
+}
+
+int nrf_mesh_attributes(nrf_context* c, float h, void* stream, nrf_mesh_attr* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  STAGE_PROLOGUE();  // (a mesh made from a caller's lattice on a context without a model has no network to ask: NRF_E_STATE)
+  auto& m = c->mesh;
+  if (!m.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  if (!points_step_valid(h, c->desc.bound)) return fail(NRF_E_INVALID, "nrf_mesh_attributes: h must be finite, > 0 and <= bound");
+  m.have_attr = false;
+  const uint64_t nv = m.n_vertices;
+  if (nv) {
+    if ((rc = grow_mesh_buffer(&m.normals, m.cap_normals, nv * 16))) return rc;
+    if ((rc = grow_mesh_buffer(&m.colors, m.cap_colors, nv * 16))) return rc;
+    HIP_TRY(launch_attributes(c, m.vertices, nullptr, (uint32_t)nv, h, m.normals, m.colors, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  m.have_attr = true;
+  out->n_vertices = nv;
+  out->normals = nv ? m.normals : nullptr;
+  out->colors = nv ? m.colors : nullptr;
+  return NRF_OK;
+}
+
+int nrf_read_mesh_attributes(nrf_context* c, float* normals, float* colors) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!c->mesh.have || !c->mesh.have_attr) return fail(NRF_E_STATE, "no attributes of the current mesh (call nrf_mesh_attributes after nrf_extract_mesh)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const auto& m = c->mesh;
+  if (normals && m.n_vertices) HIP_TRY(hipMemcpy(normals, m.normals, (size_t)m.n_vertices * 16, hipMemcpyDeviceToHost));
+  if (colors && m.n_vertices) HIP_TRY(hipMemcpy(colors, m.colors, (size_t)m.n_vertices * 16, hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

@@ -91,6 +91,18 @@ struct PointsArgs {
 hipError_t launch_points(const DevModel& M, int mode, const PointsArgs& A, hipStream_t st);
 // POINTS_VALUE at the mesh_points(L) points of a lattice (points_lattice_kernel): sigma [nx][ny][nz]; no position array is read
 hipError_t launch_points_lattice(const DevModel& M, const MeshLattice& L, float bound, float* sigma, hipStream_t st);
+// Point attributes (nrf_kernels_attr.hip, arithmetic: nrf_attr_plan.h on top of nrf_points_plan.h): the unit normal of the density
+// and the colour of the full network at points, seven network passes per chunk in one launch.  dir == nullptr: a point is looked at
+// along d = -n.  Launch sizes and LDS are launch_network's for the model's stage instance.
+struct AttrArgs {
+  const float* xyz = nullptr;  // [n][3]
+  const float* dir = nullptr;  // [n][3] or nullptr
+  uint32_t n = 0;
+  float bound = 0.f, h = 0.f, inv2h = 0.f;
+  float* normal = nullptr;  // [n][4] = (n_x, n_y, n_z, sigma)
+  float* color = nullptr;   // [n][4] = (r, g, b, |g|)
+};
+hipError_t launch_attr(const DevModel& M, const AttrArgs& A, hipStream_t st);
 // Mesh extraction (nrf_kernels_mesh.hip, arithmetic: nrf_mesh_plan.h) on a lattice of n = mesh_points(L) sigmas:
 //   launch_mesh_count  codes[n] (mesh_count_point), then vbase[n] / tbase[n] = the exclusive prefix sums of the codes' vertex and
 //                      triangle counts and totals[0 .. 1] = the sums; partials: mesh_scan_tiles(n) uint2 of workspace

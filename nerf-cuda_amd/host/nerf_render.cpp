@@ -5,6 +5,7 @@
 #include "nerf_render.h"
 
 #include "json_lite.h"
+#include "../csrc/nrf_attr_plan.h"  // (device-free: the 8-bit rule of an exported colour)
 
 #include <algorithm>
 #include <cctype>
@@ -640,6 +641,60 @@ bool NerfRender::save_obj(const std::string& path, const std::vector<float>& ver
     if (with_normals) std::fprintf(f, "f %lu//%lu %lu//%lu %lu//%lu\n", a, a, b, b, c, c);
     else std::fprintf(f, "f %lu %lu %lu\n", a, b, c);
   }
+  const bool ok = !std::ferror(f);
+  return std::fclose(f) == 0 && ok;
+}
+
+NerfRender::MeshAttributes NerfRender::mesh_attributes(float h) {
+  if (!m_have_network) throw std::runtime_error{"mesh_attributes: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"mesh_attributes: single-device renderers only"};
+  nrf_mesh_attr a{};
+  check(nrf_mesh_attributes(m_ctx[0], h, nullptr, &a), "nrf_mesh_attributes");
+  const size_t n = (size_t)a.n_vertices;
+  std::vector<float> nrm(4 * n), col(4 * n);
+  check(nrf_read_mesh_attributes(m_ctx[0], nrm.data(), col.data()), "nrf_read_mesh_attributes");
+  MeshAttributes out;
+  out.normals.resize(3 * n);
+  out.colors.resize(3 * n);
+  out.sigmas.resize(n);
+  out.lengths.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    for (int k = 0; k < 3; ++k) out.normals[3 * i + k] = nrm[4 * i + k], out.colors[3 * i + k] = col[4 * i + k];
+    out.sigmas[i] = nrm[4 * i + 3];
+    out.lengths[i] = col[4 * i + 3];
+  }
+  return out;
+}
+
+bool NerfRender::save_ply(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
+                          const std::vector<float>& normals, const std::vector<float>& colors) {
+  const size_t nv = vertices.size() / 3, nt = triangles.size() / 3;
+  if (normals.size() != 3 * nv || colors.size() != 3 * nv) return false;
+  const uint16_t probe = 1;
+  if (*reinterpret_cast<const unsigned char*>(&probe) != 1) return false;  // (the records below are written as this host holds them)
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) return false;
+  std::fprintf(f,
+               "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+               "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+               "element face %zu\nproperty list uchar int vertex_indices\nend_header\n",
+               nv, nt);
+  std::vector<unsigned char> rec(27 * nv);
+  for (size_t i = 0; i < nv; ++i) {
+    unsigned char* r = rec.data() + 27 * i;
+    std::memcpy(r, &vertices[3 * i], 12);
+    std::memcpy(r + 12, &normals[3 * i], 12);
+    for (int k = 0; k < 3; ++k) r[24 + k] = nrf::attr_color_u8(colors[3 * i + k]);
+  }
+  if (!rec.empty()) std::fwrite(rec.data(), 1, rec.size(), f);
+  rec.assign(13 * nt, 0);
+  for (size_t i = 0; i < nt; ++i) {
+    unsigned char* r = rec.data() + 13 * i;
+    r[0] = 3;
+    const int32_t idx[3] = {(int32_t)triangles[3 * i], (int32_t)triangles[3 * i + 1], (int32_t)triangles[3 * i + 2]};
+    std::memcpy(r + 1, idx, 12);
+  }
+  if (!rec.empty()) std::fwrite(rec.data(), 1, rec.size(), f);
   const bool ok = !std::ferror(f);
   return std::fclose(f) == 0 && ok;
 }

@@ -119,6 +119,19 @@ class NerfRender {
   // with normals, "f a b c" without).  Returns false when the file cannot be written.
   static bool save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
                        const std::vector<float>& normals = {});
+  // nrf_mesh_attributes (nerfhip.h): unit normals and colours at the vertices of the last extract_mesh, in one launch on the device
+  // -> host normals [n][3] (outward, -g / |g|; zeros where the gradient is degenerate), colours [n][3] (the network's rgb, looked at
+  // along -normal), sigmas [n] and |g| [n].  h is the step of the central differences; a vertex within h of the box's faces gets
+  // zeros throughout.  Synchronous; single device.
+  struct MeshAttributes {
+    std::vector<float> normals, colors, sigmas, lengths;
+  };
+  MeshAttributes mesh_attributes(float h);
+  // Binary little-endian PLY: per vertex "x y z nx ny nz" as float and "red green blue" as uchar -- a colour byte is the library's
+  // 8-bit rule (nerfhip.h: (unsigned char)(255.0 * x), saturating, NaN -> 0) --, faces as "list uchar int vertex_indices".  normals and
+  // colors are [n][3], one per vertex.  Returns false when they are not, or when the file cannot be written.
+  static bool save_ply(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
+                       const std::vector<float>& normals, const std::vector<float>& colors);
   // the density grid from the network (nerf_render.cu:388-429, dead and incomplete in the reference; completed in
   // nrf_generate_density_grid); reload_network_from_file calls it for a snapshot that carries no density grid
   void generate_density_grid();

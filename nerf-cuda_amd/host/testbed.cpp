@@ -4,8 +4,9 @@
 //   usage: testbed [snapshot.msgpack] [width height] [out_prefix] [transforms.json]
 // With a transforms.json (NeRF-synthetic / instant-ngp camera path) every frame of the path is rendered as well, in
 // batches of 32 views per launch, and written to <out_prefix>path_NNNN.rgb.
-//   options (anywhere): --save_mesh FILE.obj [--mesh_res N] [--mesh_iso X] -- the iso-surface of the density on an N^3 lattice over the
-//   model's aabb (NerfRender::extract_mesh; defaults 128 and 2.5), written as a Wavefront OBJ
+//   options (anywhere): --save_mesh FILE.obj | FILE.ply [--mesh_res N] [--mesh_iso X] -- the iso-surface of the density on an N^3 lattice
+//   over the model's aabb (NerfRender::extract_mesh; defaults 128 and 2.5), written as a Wavefront OBJ with vertex normals or, for a
+//   name that ends in .ply, as a binary PLY with vertex normals and colours (NerfRender::mesh_attributes, save_ply)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -115,16 +116,25 @@ int main(int argc, char** argv) {
       const auto m1 = std::chrono::steady_clock::now();
       std::printf("mesh: %u^3 lattice at iso %g: %zu vertices, %zu triangles, %f s\n", n, mesh_iso, mesh.vertices.size() / 3,
                   mesh.triangles.size() / 3, std::chrono::duration<double>(m1 - m0).count());
-      // vertex normals: nrf_density_gradient takes the device vertices as they are; its records need n float4 of device memory,
-      // which an n x 1 render buffer's accumulate plane is
-      std::vector<float> normals;
-      if (!mesh.vertices.empty()) {
-        RenderBuffer records;
-        records.resize(Vector2i((int)(mesh.vertices.size() / 3), 1));
-        render->density_gradient(mesh.vertices_dev, (uint32_t)(mesh.vertices.size() / 3), b / 128.0f, records.accumulate_buffer());
-        normals = NerfRender::normals_from_gradients(records.accumulate_buffer_host());
+      if (mesh_path.size() >= 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0) {
+        // normals and colours in one launch at the device vertices (a vertex within the step of the box's faces gets zeros)
+        const auto a0 = std::chrono::steady_clock::now();
+        const NerfRender::MeshAttributes attr = render->mesh_attributes(b / 128.0f);
+        const auto a1 = std::chrono::steady_clock::now();
+        std::printf("mesh attributes: %zu vertices, %f s\n", attr.sigmas.size(), std::chrono::duration<double>(a1 - a0).count());
+        if (!NerfRender::save_ply(mesh_path, mesh.vertices, mesh.triangles, attr.normals, attr.colors)) throw std::runtime_error{"cannot write " + mesh_path};
+      } else {
+        // OBJ, vertex normals: nrf_density_gradient takes the device vertices as they are; its records need n float4 of device memory,
+        // which an n x 1 render buffer's accumulate plane is
+        std::vector<float> normals;
+        if (!mesh.vertices.empty()) {
+          RenderBuffer records;
+          records.resize(Vector2i((int)(mesh.vertices.size() / 3), 1));
+          render->density_gradient(mesh.vertices_dev, (uint32_t)(mesh.vertices.size() / 3), b / 128.0f, records.accumulate_buffer());
+          normals = NerfRender::normals_from_gradients(records.accumulate_buffer_host());
+        }
+        if (!NerfRender::save_obj(mesh_path, mesh.vertices, mesh.triangles, normals)) throw std::runtime_error{"cannot write " + mesh_path};
       }
-      if (!NerfRender::save_obj(mesh_path, mesh.vertices, mesh.triangles, normals)) throw std::runtime_error{"cannot write " + mesh_path};
     }
     delete render;
   } catch (const std::exception& e) {

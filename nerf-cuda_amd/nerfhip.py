@@ -170,6 +170,15 @@ class Mesh(C.Structure):
     ]
 
 
+class MeshAttr(C.Structure):
+    """nrf_mesh_attr: device pointers owned by the context, valid until the next extract_mesh, mesh_attributes or close."""
+    _fields_ = [
+        ("n_vertices", C.c_uint64),
+        ("normals", C.c_void_p),  # float4 [n_vertices] = (n_x, n_y, n_z, sigma)
+        ("colors", C.c_void_p),   # float4 [n_vertices] = (r, g, b, |g|)
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64),
@@ -292,6 +301,9 @@ _SIGS = {
     "nrf_density_lattice": (C.c_int, [C.c_void_p, C.POINTER(Lattice), C.c_void_p, C.c_void_p]),
     "nrf_extract_mesh": (C.c_int, [C.c_void_p, C.POINTER(Lattice), C.c_float, C.c_void_p, C.c_void_p, C.POINTER(Mesh)]),
     "nrf_read_mesh": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "nrf_point_attributes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_mesh_attributes": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.POINTER(MeshAttr)]),
+    "nrf_read_mesh_attributes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -873,6 +885,28 @@ class NerfHip:
         v, t = np.empty((nv, 3), np.float32), np.empty((nt, 3), np.uint32)
         _check(self.lib.nrf_read_mesh(self.h, v.ctypes.data_as(C.POINTER(C.c_float)), t.ctypes.data_as(C.POINTER(C.c_uint32))))
         return v, t
+
+    def point_attributes(self, xyz_ptr, n, h, normal_ptr, color_ptr, dir_ptr=0, stream=None):
+        """nrf_point_attributes: normal (device float4 [n]) = (n_x, n_y, n_z, sigma), color (device float4 [n]) = (r, g, b, |g|) at n
+        points (device fp32 [n][3]): n = -g / |g| of density_gradient's record, sigma and rgb those of network() at the point, looked
+        at along dir (device fp32 [n][3]) or, dir_ptr 0, along -n.  A point the guard of density_gradient refuses yields zeros."""
+        _check(self.lib.nrf_point_attributes(self.h, C.c_void_p(xyz_ptr), C.c_void_p(dir_ptr or 0), int(n), C.c_float(h),
+                                             C.c_void_p(normal_ptr), C.c_void_p(color_ptr), C.c_void_p(stream or 0)))
+
+    def mesh_attributes(self, h: float, stream=None) -> MeshAttr:
+        """nrf_mesh_attributes: point_attributes at the vertices of the last extract_mesh, into buffers of the context.  Returns
+        after completion."""
+        out = MeshAttr()
+        _check(self.lib.nrf_mesh_attributes(self.h, C.c_float(h), C.c_void_p(stream or 0), C.byref(out)))
+        self._mesh_attr_count = int(out.n_vertices)
+        return out
+
+    def read_mesh_attributes(self):
+        """nrf_read_mesh_attributes: (normals float32 [n_vertices][4], colors float32 [n_vertices][4]) of the last mesh_attributes"""
+        nv = getattr(self, "_mesh_attr_count", 0)
+        nrm, col = np.empty((nv, 4), np.float32), np.empty((nv, 4), np.float32)
+        _check(self.lib.nrf_read_mesh_attributes(self.h, nrm.ctypes.data_as(C.POINTER(C.c_float)), col.ctypes.data_as(C.POINTER(C.c_float))))
+        return nrm, col
 
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
