@@ -646,6 +646,49 @@ int nrf_point_attributes(nrf_context* ctx, const void* xyz, const void* dir, uin
                          void* stream);
 int nrf_mesh_attributes(nrf_context* ctx, float h, void* stream, nrf_mesh_attr* out);
 int nrf_read_mesh_attributes(nrf_context* ctx, float* normals_f32x4, float* colors_f32x4);
+/* (ABI 7, addition) Connected components and floater removal: an iso-surface of a trained density is never one surface -- it is the
+ * object plus small closed blobs around it and, on a lattice that spans the whole box, open sheets at the faces.  These calls label
+ * the components of the context's current mesh on the device, report a small table of them and filter the mesh in place by component
+ * size, so that "the object" never travels to the host and back before it gets its attributes.  Integers and copied float bits only:
+ *   connected  two vertices of the current mesh are connected if a triangle names both; components are the classes of the transitive
+ *              closure.  A vertex that no triangle names is a component of its own with 0 triangles (nrf_extract_mesh never makes one).
+ *   label      label[v] = the smallest vertex id in v's component; hence label[v] <= v and label[label[v]] == label[v], and the result
+ *              does not depend on the order in which anything ran.
+ *   table      one row per component in ascending label: label, n_vertices, n_triangles.  A triangle belongs to the component of its
+ *              vertices.  The counts are integer sums and exact.
+ *   keep       a component is kept iff n_triangles >= min_triangles; with NRF_MESH_KEEP_LARGEST it must in addition be the component
+ *              with the most triangles, a tie going to the smaller label.  With the flag set and min_triangles above the largest count
+ *              nothing is kept.
+ *   filtered   a vertex is kept iff its component is, a triangle likewise.  Kept vertices keep their float bits and their relative
+ *              order: the new id of a vertex is the number of kept vertices with a smaller old id.  Kept triangles keep their relative
+ *              order and the order of their three indices, each index remapped.  (csrc/nrf_meshcc_plan.h is this text as code.)
+ * nrf_mesh_components: labels and table of the current mesh, in buffers owned by the context that grow as needed and stay valid until
+ *   the next nrf_extract_mesh, nrf_filter_mesh, nrf_mesh_components or nrf_destroy.  n_rounds reports how many hook + compress rounds
+ *   the labelling took, the final round that changed nothing included.  An empty mesh is NRF_OK with n_components == 0.
+ * nrf_read_mesh_components: host copies of the current labelling: uint32 [n_vertices] and uint32 [n_components][3]; either may be NULL.
+ * nrf_filter_mesh: the context's mesh BECOMES the filtered mesh -- nrf_read_mesh, nrf_mesh_attributes and nrf_point_attributes on
+ *   out->vertices all see it; out->sigma is the extraction's, unchanged; earlier vertices / triangles pointers are invalid.  It labels
+ *   the mesh itself when no current labelling exists.  Keeping everything leaves the mesh bit for bit as it was; keeping nothing is
+ *   NRF_OK with zero counts.  It invalidates the labelling and the attributes of the mesh it replaced: nrf_read_mesh_components and
+ *   nrf_read_mesh_attributes return NRF_E_STATE until asked again -- attributes after filtering is the intended order: fewer vertices,
+ *   seven network passes each.
+ * The work is enqueued on `stream` (NULL: the context's) and the calls return after it has completed, as nrf_extract_mesh does: sizes
+ * and the labelling's convergence flag have to reach the host.  No model is needed.  NRF_E_INVALID: a NULL out; an unknown flag bit.
+ * NRF_E_STATE: no mesh extracted yet; nrf_read_mesh_components: no current labelling.  NRF_E_HIP with a message: the mesh changed
+ * between the scan and the scatter pass of the filter (every write is checked against the counted sizes).  A refused call writes
+ * nothing.  The calls take no slot of the 16 calls in flight, leave nrf_get_stats untouched and write none of the context's frame
+ * buffers. */
+typedef struct nrf_mesh_parts {
+  uint64_t n_components;
+  void* labels;        /* device uint32 [n_vertices]: label of each vertex of the current mesh                 */
+  void* components;    /* device uint32 [n_components][3] = label, n_vertices, n_triangles; ascending label    */
+  uint32_t n_rounds;   /* hook + compress rounds the labelling took, the final round that changed nothing included */
+  uint32_t reserved;   /* written as 0 */
+} nrf_mesh_parts;
+enum { NRF_MESH_KEEP_LARGEST = 1 };  /* nrf_filter_mesh flags */
+int nrf_mesh_components(nrf_context* ctx, void* stream, nrf_mesh_parts* out);
+int nrf_read_mesh_components(nrf_context* ctx, uint32_t* labels, uint32_t* components);
+int nrf_filter_mesh(nrf_context* ctx, uint64_t min_triangles, uint32_t flags, void* stream, nrf_mesh* out);
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

@@ -23,6 +23,7 @@
 #include "nrf_generic.h"
 #include "nrf_grid_plan.h"
 #include "nrf_launch.h"
+#include "nrf_meshcc_plan.h"
 #include "nrf_model_plan.h"
 #include "nrf_points_plan.h"
 
@@ -164,6 +165,16 @@ struct nrf_context {
     void *normals = nullptr, *colors = nullptr;
     size_t cap_normals = 0, cap_colors = 0;
     bool have_attr = false;
+    // nrf_mesh_components / nrf_filter_mesh: the labelling and the table of the mesh above (have_parts falls with every
+    // nrf_extract_mesh and nrf_filter_mesh), the second vertex / triangle buffers the filter scatters into and then swaps in, and
+    // cc_words (device): the largest component's key (64 bits), the hook's changed flag, the scatter's flag, a scan's two totals
+    void *labels = nullptr, *rows = nullptr, *components = nullptr, *vertices2 = nullptr, *triangles2 = nullptr;
+    size_t cap_labels = 0, cap_rows = 0, cap_components = 0, cap_vertices2 = 0, cap_triangles2 = 0;
+    uint32_t* cc_words = nullptr;
+    uint64_t n_components = 0;
+    uint32_t n_rounds = 0;
+    bool have_parts = false;
+    void* sigma_used = nullptr;  // nrf_mesh.sigma of the extraction
   } mesh;
 };
 
@@ -225,7 +236,8 @@ void free_frame(nrf_context* c) {
 
 void free_mesh(nrf_context* c) {
   auto& m = c->mesh;
-  for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, m.normals, m.colors, (void*)m.totals})
+  for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, m.normals, m.colors, (void*)m.totals,
+                  m.labels, m.rows, m.components, m.vertices2, m.triangles2, (void*)m.cc_words})
     if (q) (void)hipFree(q);
   m = nrf_context::MeshBuffers{};
 }
@@ -1840,6 +1852,7 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   auto& m = c->mesh;
   m.have = false;
   m.have_attr = false;
+  m.have_parts = false;
   const uint64_t n = mesh_points(L);
   if ((rc = grow_mesh_buffer(&m.codes, m.cap_codes, n * 4))) return rc;
   if ((rc = grow_mesh_buffer(&m.vbase, m.cap_vbase, n * 4))) return rc;
@@ -1869,11 +1882,12 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   m.n_vertices = nv;
   m.n_triangles = nt;
   m.have = true;
+  m.sigma_used = const_cast<float*>(s);
   out->n_vertices = nv;
   out->n_triangles = nt;
   out->vertices = nv ? m.vertices : nullptr;
   out->triangles = nt ? m.triangles : nullptr;
-  out->sigma = const_cast<float*>(s);
+  out->sigma = m.sigma_used;
   return NRF_OK;
 }
 
@@ -1885,6 +1899,168 @@ int nrf_read_mesh(nrf_context* c, float* vertices, uint32_t* triangles) {
   const auto& m = c->mesh;
   if (vertices && m.n_vertices) HIP_TRY(hipMemcpy(vertices, m.vertices, (size_t)mesh_vertex_bytes(m.n_vertices), hipMemcpyDeviceToHost));
   if (triangles && m.n_triangles) HIP_TRY(hipMemcpy(triangles, m.triangles, (size_t)mesh_triangle_bytes(m.n_triangles), hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// Connected components and the filter by component size (nrf_kernels_meshcc.hip; the definition is nrf_meshcc_plan.h's).  Like the
+// extraction: no slot of the 16-call ring, no statistics, no frame buffer, and no model.
+namespace {
+// the scan workspace of the extraction, for n code words (its contents are the extraction's no longer)
+int grow_mesh_scan(nrf_context* c, uint64_t n) {
+  auto& m = c->mesh;
+  int rc;
+  if ((rc = grow_mesh_buffer(&m.codes, m.cap_codes, n * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.vbase, m.cap_vbase, n * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.tbase, m.cap_tbase, n * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.partials, m.cap_partials, (uint64_t)mesh_scan_tiles((uint32_t)n) * 8))) return rc;
+  if (!m.cc_words) HIP_TRY(hipMalloc((void**)&m.cc_words, 32));
+  return NRF_OK;
+}
+
+MeshccArgs meshcc_args(const nrf_context* c) {
+  const auto& m = c->mesh;
+  MeshccArgs A;
+  A.n_vertices = (uint32_t)m.n_vertices;
+  A.n_triangles = (uint32_t)m.n_triangles;
+  A.triangles = (const uint32_t*)m.triangles;
+  A.labels = (uint32_t*)m.labels;
+  A.rows = (uint32_t*)m.rows;
+  A.components = (uint32_t*)m.components;
+  A.n_components = (uint32_t)m.n_components;
+  A.best = (unsigned long long*)m.cc_words;
+  return A;
+}
+
+// labels, rows and the table of the current mesh; returns after completion
+int label_mesh(nrf_context* c, hipStream_t st) {
+  auto& m = c->mesh;
+  m.have_parts = false;
+  m.n_components = 0;
+  m.n_rounds = 0;
+  const uint64_t nv = m.n_vertices, nt = m.n_triangles;
+  if (!nv) {
+    m.have_parts = true;
+    return NRF_OK;
+  }
+  int rc;
+  if ((rc = grow_mesh_scan(c, nv > nt ? nv : nt))) return rc;
+  if ((rc = grow_mesh_buffer(&m.labels, m.cap_labels, nv * 4))) return rc;
+  if ((rc = grow_mesh_buffer(&m.rows, m.cap_rows, nv * 4))) return rc;
+  MeshccArgs A = meshcc_args(c);
+  HIP_TRY(launch_meshcc_init(A, st));
+  // hook + compress until a hook lowered nothing: the flag (4 bytes) reaches the host after every round.  A changing round removes a
+  // root, so n_vertices + 1 rounds are the most a mesh can take (nrf_kernels_meshcc.hip)
+  uint32_t rounds = 0;
+  for (;;) {
+    uint32_t changed = 0;
+    HIP_TRY(hipMemsetAsync(m.cc_words + 2, 0, 4, st));
+    HIP_TRY(launch_meshcc_round(A, m.cc_words + 2, st));
+    HIP_TRY(hipMemcpyAsync(&changed, m.cc_words + 2, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ++rounds;
+    if (!changed) break;
+    if (rounds > nv) return fail(NRF_E_HIP, "nrf_mesh_components: the labelling did not settle within n_vertices + 1 rounds");
+  }
+  // root flags -> rows (the vertex channel of the mesh scan; its triangle channel is all zeros) and the number of components
+  uint32_t totals[2] = {0, 0};
+  HIP_TRY(launch_meshcc_roots(A, (uint32_t*)m.codes, st));
+  HIP_TRY(launch_mesh_scan((const uint32_t*)m.codes, (uint32_t)nv, (uint32_t*)m.rows, (uint32_t*)m.tbase, m.partials, m.cc_words + 4, st));
+  HIP_TRY(hipMemcpyAsync(totals, m.cc_words + 4, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t nc = totals[0];
+  if (!nc || nc > nv) return fail(NRF_E_HIP, "nrf_mesh_components: the root count is out of range");
+  if ((rc = grow_mesh_buffer(&m.components, m.cap_components, nc * 12))) return rc;
+  HIP_TRY(hipMemsetAsync(m.components, 0, (size_t)nc * 12, st));
+  HIP_TRY(hipMemsetAsync(m.cc_words, 0, 8, st));
+  m.n_components = nc;
+  A = meshcc_args(c);
+  HIP_TRY(launch_meshcc_table(A, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  m.n_rounds = rounds;
+  m.have_parts = true;
+  return NRF_OK;
+}
+}  // namespace
+
+int nrf_mesh_components(nrf_context* c, void* stream, nrf_mesh_parts* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (!c->mesh.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if ((rc = label_mesh(c, st))) {
+    c->mesh.have_parts = false;
+    return rc;
+  }
+  const auto& m = c->mesh;
+  out->n_components = m.n_components;
+  out->labels = m.n_vertices ? m.labels : nullptr;
+  out->components = m.n_components ? m.components : nullptr;
+  out->n_rounds = m.n_rounds;
+  out->reserved = 0;
+  return NRF_OK;
+}
+
+int nrf_read_mesh_components(nrf_context* c, uint32_t* labels, uint32_t* components) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!c->mesh.have || !c->mesh.have_parts)
+    return fail(NRF_E_STATE, "no components of the current mesh (call nrf_mesh_components after nrf_extract_mesh or nrf_filter_mesh)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const auto& m = c->mesh;
+  if (labels && m.n_vertices) HIP_TRY(hipMemcpy(labels, m.labels, (size_t)m.n_vertices * 4, hipMemcpyDeviceToHost));
+  if (components && m.n_components) HIP_TRY(hipMemcpy(components, m.components, (size_t)m.n_components * 12, hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+int nrf_filter_mesh(nrf_context* c, uint64_t min_triangles, uint32_t flags, void* stream, nrf_mesh* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (!meshcc_flags_valid(flags)) return fail(NRF_E_INVALID, "nrf_filter_mesh: unknown flag bit");
+  auto& m = c->mesh;
+  if (!m.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  if (!m.have_parts && (rc = label_mesh(c, st))) {
+    m.have_parts = false;
+    return rc;
+  }
+  uint32_t kept[2] = {0, 0};
+  if (m.n_vertices) {
+    const uint64_t nv = m.n_vertices, nt = m.n_triangles, n = nv > nt ? nv : nt;
+    const MeshccArgs A = meshcc_args(c);
+    // keep flags; the two prefix sums; the kept sizes reach the host; scatter into second buffers of exactly checked sizes; the flag
+    // reaches the host; then the second buffers ARE the mesh
+    HIP_TRY(launch_meshcc_keep(A, min_triangles, flags, (uint32_t*)m.codes, st));
+    HIP_TRY(launch_mesh_scan((const uint32_t*)m.codes, (uint32_t)n, (uint32_t*)m.vbase, (uint32_t*)m.tbase, m.partials, m.cc_words + 4, st));
+    HIP_TRY(hipMemsetAsync(m.cc_words + 3, 0, 4, st));
+    HIP_TRY(hipMemcpyAsync(kept, m.cc_words + 4, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (kept[0] > nv || kept[1] > nt) return fail(NRF_E_HIP, "nrf_filter_mesh: the kept counts exceed the mesh");
+    if ((rc = grow_mesh_buffer(&m.vertices2, m.cap_vertices2, mesh_vertex_bytes(kept[0])))) return rc;
+    if ((rc = grow_mesh_buffer(&m.triangles2, m.cap_triangles2, mesh_triangle_bytes(kept[1])))) return rc;
+    uint32_t dropped = 0;
+    HIP_TRY(launch_meshcc_scatter(A, (const float*)m.vertices, (const uint32_t*)m.codes, (const uint32_t*)m.vbase, (const uint32_t*)m.tbase, kept[0],
+                                  kept[1], (float*)m.vertices2, (uint32_t*)m.triangles2, m.cc_words + 3, st));
+    HIP_TRY(hipMemcpyAsync(&dropped, m.cc_words + 3, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (dropped) return fail(NRF_E_HIP, "nrf_filter_mesh: the scan and the scatter pass disagree (the mesh changed during the call); writes were dropped");
+    std::swap(m.vertices, m.vertices2);
+    std::swap(m.cap_vertices, m.cap_vertices2);
+    std::swap(m.triangles, m.triangles2);
+    std::swap(m.cap_triangles, m.cap_triangles2);
+    m.n_vertices = kept[0];
+    m.n_triangles = kept[1];
+  }
+  m.have_parts = false;
+  m.have_attr = false;
+  out->n_vertices = m.n_vertices;
+  out->n_triangles = m.n_triangles;
+  out->vertices = m.n_vertices ? m.vertices : nullptr;
+  out->triangles = m.n_triangles ? m.triangles : nullptr;
+  out->sigma = m.sigma_used;
   return NRF_OK;
 }
 

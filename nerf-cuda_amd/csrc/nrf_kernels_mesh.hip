@@ -4,6 +4,7 @@
 //   mesh_count_kernel          per lattice point: the crossing mask of its seven edges and the triangle count of its cell (one code word)
 //   mesh_scan_{reduce,partials,write}_kernel   the two exclusive prefix sums of the codes' counts, three passes over tiles of
 //                              MESH_SCAN_TILE points: tile sums, the scan of the tile sums (one workgroup), the scan inside the tiles
+//                              (launch_mesh_scan: also the scan of nrf_kernels_meshcc.hip, over code words that decode to 0 / 1)
 //   mesh_emit_kernel           the vertices and the triangles at their scanned offsets; every write is checked against the element
 //                              counts the buffers hold, a write that would fall outside is dropped and raises *flag
 // Streaming kernels: a lattice point reads its cell's eight sigmas (count, emit) and, where its cell has triangles, the codes and
@@ -137,8 +138,15 @@ static uint32_t mesh_groups(uint32_t n) {
 hipError_t launch_mesh_count(const MeshLattice& L, const float* sigma, float iso, uint32_t* codes, uint32_t* vbase, uint32_t* tbase,
                              void* partials, uint32_t* totals, hipStream_t st) {
   if (!mesh_lattice_valid(L.origin, L.cell, L.dims) || !sigma || !codes || !vbase || !tbase || !partials || !totals) return hipErrorInvalidValue;
-  const uint32_t n = mesh_points(L), tiles = mesh_scan_tiles(n);
+  const uint32_t n = mesh_points(L);
   hipLaunchKernelGGL(mesh_count_kernel, dim3(mesh_groups(n)), dim3(MESH_BLOCK), 0, st, L, sigma, iso, n, codes);
+  return launch_mesh_scan(codes, n, vbase, tbase, partials, totals, st);
+}
+
+hipError_t launch_mesh_scan(const uint32_t* codes, uint32_t n, uint32_t* vbase, uint32_t* tbase, void* partials, uint32_t* totals,
+                            hipStream_t st) {
+  if (!n || !codes || !vbase || !tbase || !partials || !totals) return hipErrorInvalidValue;
+  const uint32_t tiles = mesh_scan_tiles(n);
   hipLaunchKernelGGL(mesh_scan_reduce_kernel, dim3(tiles), dim3(MESH_BLOCK), 0, st, codes, n, (uint2*)partials);
   hipLaunchKernelGGL(mesh_scan_partials_kernel, dim3(1), dim3(MESH_BLOCK), 0, st, (uint2*)partials, tiles, totals);
   hipLaunchKernelGGL(mesh_scan_write_kernel, dim3(tiles), dim3(MESH_BLOCK), 0, st, codes, n, (const uint2*)partials, vbase, tbase);

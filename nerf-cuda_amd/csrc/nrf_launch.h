@@ -115,6 +115,37 @@ hipError_t launch_mesh_count(const MeshLattice& L, const float* sigma, float iso
 hipError_t launch_mesh_emit(const MeshLattice& L, const float* sigma, float iso, const uint32_t* codes, const uint32_t* vbase,
                             const uint32_t* tbase, uint32_t n_vertices, uint32_t n_triangles, float* vertices, uint32_t* triangles,
                             uint32_t* flag, hipStream_t st);
+//   launch_mesh_scan   the scan of launch_mesh_count by itself, over any n > 0 code words: vbase[n] / tbase[n] = the exclusive prefix
+//                      sums of mesh_code_vertices / mesh_code_triangles of the codes, totals[0 .. 1] = the sums
+hipError_t launch_mesh_scan(const uint32_t* codes, uint32_t n, uint32_t* vbase, uint32_t* tbase, void* partials, uint32_t* totals,
+                            hipStream_t st);
+// Connected components and the filter by component size of an indexed mesh (nrf_kernels_meshcc.hip, definition: nrf_meshcc_plan.h);
+// n_vertices > 0.  Every launch is a streaming pass that needs nothing another workgroup writes during it.
+//   launch_meshcc_init      parent[v] = v
+//   launch_meshcc_round     hook over the triangles (*changed = 1 when an atomic minimum lowered a parent), then compress over the vertices
+//   launch_meshcc_roots     codes[v] = a scan code word whose vertex channel is 1 where parent[v] == v (launch_mesh_scan makes the rows of it)
+//   launch_meshcc_table     components [n_components][3] (zeroed by the caller) = (label, n_vertices, n_triangles) by integer atomic adds,
+//                           then *best = the maximum of meshcc_key over the rows (zeroed by the caller)
+//   launch_meshcc_keep      codes[i], i < max(n_vertices, n_triangles): the keep flags of vertex i and triangle i as a scan code word
+//   launch_meshcc_scatter   the kept vertices and the remapped kept triangles into second buffers of kept_vertices / kept_triangles
+//                           elements; *flag is set to 1 when a write was dropped because it would have fallen outside those counts
+struct MeshccArgs {
+  uint32_t n_vertices = 0, n_triangles = 0;
+  const uint32_t* triangles = nullptr;  // [n_triangles][3]
+  uint32_t* labels = nullptr;           // [n_vertices]: parent[] while the labelling runs, label[] after it
+  uint32_t* rows = nullptr;             // [n_vertices]: the number of roots below v
+  uint32_t* components = nullptr;       // [n_components][3]
+  uint32_t n_components = 0;
+  unsigned long long* best = nullptr;
+};
+hipError_t launch_meshcc_init(const MeshccArgs& A, hipStream_t st);
+hipError_t launch_meshcc_round(const MeshccArgs& A, uint32_t* changed, hipStream_t st);
+hipError_t launch_meshcc_roots(const MeshccArgs& A, uint32_t* codes, hipStream_t st);
+hipError_t launch_meshcc_table(const MeshccArgs& A, hipStream_t st);
+hipError_t launch_meshcc_keep(const MeshccArgs& A, uint64_t min_triangles, uint32_t flags, uint32_t* codes, hipStream_t st);
+hipError_t launch_meshcc_scatter(const MeshccArgs& A, const float* vertices, const uint32_t* codes, const uint32_t* vnew, const uint32_t* tnew,
+                                 uint32_t kept_vertices, uint32_t kept_triangles, float* vertices_out, uint32_t* triangles_out, uint32_t* flag,
+                                 hipStream_t st);
 hipError_t launch_density_positions(uint32_t H, float k, void* xyz, void* dir, hipStream_t st);
 hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int n_iterations, void* grid, hipStream_t st);
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,

@@ -623,6 +623,32 @@ NerfRender::Mesh NerfRender::extract_mesh(const float origin[3], const float cel
   out.triangles.resize(3 * (size_t)m.n_triangles);
   check(nrf_read_mesh(m_ctx[0], out.vertices.data(), out.triangles.data()), "nrf_read_mesh");
   out.vertices_dev = m.vertices;
+  m_mesh_vertices = (size_t)m.n_vertices;
+  return out;
+}
+
+NerfRender::MeshComponents NerfRender::mesh_components() {
+  if (m_ctx.size() != 1) throw std::runtime_error{"mesh_components: single-device renderers only"};
+  nrf_mesh_parts p{};
+  check(nrf_mesh_components(m_ctx[0], nullptr, &p), "nrf_mesh_components");
+  MeshComponents out;
+  out.labels.resize(m_mesh_vertices);
+  out.table.resize(3 * (size_t)p.n_components);
+  out.rounds = p.n_rounds;
+  check(nrf_read_mesh_components(m_ctx[0], out.labels.data(), out.table.data()), "nrf_read_mesh_components");
+  return out;
+}
+
+NerfRender::Mesh NerfRender::filter_mesh(uint64_t min_triangles, bool keep_largest) {
+  if (m_ctx.size() != 1) throw std::runtime_error{"filter_mesh: single-device renderers only"};
+  nrf_mesh m{};
+  check(nrf_filter_mesh(m_ctx[0], min_triangles, keep_largest ? (uint32_t)NRF_MESH_KEEP_LARGEST : 0u, nullptr, &m), "nrf_filter_mesh");
+  Mesh out;
+  out.vertices.resize(3 * (size_t)m.n_vertices);
+  out.triangles.resize(3 * (size_t)m.n_triangles);
+  check(nrf_read_mesh(m_ctx[0], out.vertices.data(), out.triangles.data()), "nrf_read_mesh");
+  out.vertices_dev = m.vertices;
+  m_mesh_vertices = (size_t)m.n_vertices;
   return out;
 }
 

@@ -115,6 +115,18 @@ class NerfRender {
     const void* vertices_dev = nullptr;
   };
   Mesh extract_mesh(const float origin[3], const float cell[3], const uint32_t dims[3], float iso);
+  // nrf_mesh_components (nerfhip.h): the connected components of the last extract_mesh / filter_mesh, labelled on the device -> host
+  // labels [n] (the smallest vertex id of each vertex's component) and table [c][3] = (label, vertices, triangles) in ascending label;
+  // rounds = the hook + compress rounds the labelling took.  Synchronous; single device.
+  struct MeshComponents {
+    std::vector<uint32_t> labels, table;
+    uint32_t rounds = 0;
+  };
+  MeshComponents mesh_components();
+  // nrf_filter_mesh (nerfhip.h): keeps the components with at least min_triangles triangles -- with keep_largest only the one with the
+  // most triangles, a tie going to the smaller label -- and makes the result the context's mesh (mesh_attributes then sees it) -> the
+  // filtered mesh as extract_mesh returns one.  Synchronous; single device.
+  Mesh filter_mesh(uint64_t min_triangles, bool keep_largest);
   // Wavefront OBJ: "v x y z" per vertex, "vn x y z" per vertex when normals ([n][3]) has one per vertex, faces 1-based ("f a//a b//b c//c"
   // with normals, "f a b c" without).  Returns false when the file cannot be written.
   static bool save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
@@ -160,6 +172,7 @@ class NerfRender {
   std::string m_network_config_path;
   nrf_model_desc m_desc{};
   uint32_t m_gather_copy_budget_mb = 0;
+  size_t m_mesh_vertices = 0;  // of the context's current mesh (extract_mesh, filter_mesh)
   bool m_have_snapshot = false, m_have_network = false;
   std::vector<float> m_params, m_density_grid;
   Vector2i resolution;

@@ -7,6 +7,9 @@
 //   options (anywhere): --save_mesh FILE.obj | FILE.ply [--mesh_res N] [--mesh_iso X] -- the iso-surface of the density on an N^3 lattice
 //   over the model's aabb (NerfRender::extract_mesh; defaults 128 and 2.5), written as a Wavefront OBJ with vertex normals or, for a
 //   name that ends in .ply, as a binary PLY with vertex normals and colours (NerfRender::mesh_attributes, save_ply)
+//   [--mesh_min_triangles N] [--mesh_largest] -- between extraction and attributes the mesh is filtered on the device by connected
+//   component (NerfRender::mesh_components, filter_mesh): components with fewer than N triangles are dropped, --mesh_largest keeps only
+//   the component with the most triangles
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -28,14 +31,19 @@ int main(int argc, char** argv) {
   std::string mesh_path;
   int mesh_res = 128;
   float mesh_iso = 2.5f;  // (instant-ngp's default mesh threshold)
+  unsigned long long mesh_min_triangles = 0;
+  bool mesh_largest = false;
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
-      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso") && i + 1 < argc) {
+      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles") && i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
         else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
+        else if (a == "--mesh_min_triangles") mesh_min_triangles = std::strtoull(argv[++i], nullptr, 10);
         else mesh_iso = (float)std::atof(argv[++i]);
+      } else if (a == "--mesh_largest") {
+        mesh_largest = true;
       } else {
         argv[kept++] = argv[i];
       }
@@ -112,10 +120,26 @@ int main(int argc, char** argv) {
       const float origin[3] = {-b, -b, -b}, step = 2.0f * b / (float)(n - 1), cell[3] = {step, step, step};
       const uint32_t dims[3] = {n, n, n};
       const auto m0 = std::chrono::steady_clock::now();
-      const NerfRender::Mesh mesh = render->extract_mesh(origin, cell, dims, mesh_iso);
+      NerfRender::Mesh mesh = render->extract_mesh(origin, cell, dims, mesh_iso);
       const auto m1 = std::chrono::steady_clock::now();
       std::printf("mesh: %u^3 lattice at iso %g: %zu vertices, %zu triangles, %f s\n", n, mesh_iso, mesh.vertices.size() / 3,
                   mesh.triangles.size() / 3, std::chrono::duration<double>(m1 - m0).count());
+      if (mesh_min_triangles || mesh_largest) {
+        // floaters off, on the device, before the attributes: fewer vertices for the seven network passes each of them costs
+        const size_t nv0 = mesh.vertices.size() / 3, nt0 = mesh.triangles.size() / 3;
+        const auto f0 = std::chrono::steady_clock::now();
+        const NerfRender::MeshComponents parts = render->mesh_components();
+        mesh = render->filter_mesh(mesh_min_triangles, mesh_largest);
+        const auto f1 = std::chrono::steady_clock::now();
+        // the keep rule on the table's rows (ascending label: the first row with the most triangles wins a tie)
+        const size_t rows = parts.table.size() / 3;
+        size_t largest = 0, kept = 0;
+        for (size_t r = 1; r < rows; ++r)
+          if (parts.table[3 * r + 2] > parts.table[3 * largest + 2]) largest = r;
+        for (size_t r = 0; r < rows; ++r) kept += parts.table[3 * r + 2] >= mesh_min_triangles && (!mesh_largest || r == largest);
+        std::printf("mesh filter: %zu components, %zu kept, vertices %zu -> %zu, triangles %zu -> %zu, %f s\n", rows, kept, nv0,
+                    mesh.vertices.size() / 3, nt0, mesh.triangles.size() / 3, std::chrono::duration<double>(f1 - f0).count());
+      }
       if (mesh_path.size() >= 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0) {
         // normals and colours in one launch at the device vertices (a vertex within the step of the box's faces gets zeros)
         const auto a0 = std::chrono::steady_clock::now();

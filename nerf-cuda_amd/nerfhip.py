@@ -179,6 +179,20 @@ class MeshAttr(C.Structure):
     ]
 
 
+class MeshParts(C.Structure):
+    """nrf_mesh_parts: device pointers owned by the context, valid until the next extract_mesh, filter_mesh, mesh_components or close."""
+    _fields_ = [
+        ("n_components", C.c_uint64),
+        ("labels", C.c_void_p),      # uint32 [n_vertices]
+        ("components", C.c_void_p),  # uint32 [n_components][3] = (label, n_vertices, n_triangles), ascending label
+        ("n_rounds", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+NRF_MESH_KEEP_LARGEST = 1
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64),
@@ -304,6 +318,9 @@ _SIGS = {
     "nrf_point_attributes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_mesh_attributes": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.POINTER(MeshAttr)]),
     "nrf_read_mesh_attributes": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nrf_mesh_components": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MeshParts)]),
+    "nrf_read_mesh_components": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nrf_filter_mesh": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(Mesh)]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -907,6 +924,33 @@ class NerfHip:
         nrm, col = np.empty((nv, 4), np.float32), np.empty((nv, 4), np.float32)
         _check(self.lib.nrf_read_mesh_attributes(self.h, nrm.ctypes.data_as(C.POINTER(C.c_float)), col.ctypes.data_as(C.POINTER(C.c_float))))
         return nrm, col
+
+    def mesh_components(self, stream=None) -> MeshParts:
+        """nrf_mesh_components: the connected components of the current mesh, labelled on the device: parts.labels (uint32
+        [n_vertices], the smallest vertex id of each vertex's component) and parts.components (uint32 [n_components][3] = (label,
+        n_vertices, n_triangles), ascending label), in buffers of the context.  Returns after completion."""
+        out = MeshParts()
+        _check(self.lib.nrf_mesh_components(self.h, C.c_void_p(stream or 0), C.byref(out)))
+        self._mesh_parts_counts = (getattr(self, "_mesh_counts", (0, 0))[0], int(out.n_components))
+        return out
+
+    def read_mesh_components(self):
+        """nrf_read_mesh_components: (labels uint32 [n_vertices], components uint32 [n_components][3]) of the last mesh_components"""
+        nv, nc = getattr(self, "_mesh_parts_counts", (0, 0))
+        labels, table = np.empty(nv, np.uint32), np.empty((nc, 3), np.uint32)
+        _check(self.lib.nrf_read_mesh_components(self.h, labels.ctypes.data_as(C.POINTER(C.c_uint32)), table.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return labels, table
+
+    def filter_mesh(self, min_triangles: int = 0, keep_largest: bool = False, stream=None) -> Mesh:
+        """nrf_filter_mesh: keeps the components of the current mesh with at least min_triangles triangles -- with keep_largest only
+        the one with the most triangles, a tie going to the smaller label -- and makes the result the context's mesh: read_mesh and
+        mesh_attributes see it.  The labelling and the attributes of the mesh it replaced are invalid afterwards."""
+        out = Mesh()
+        _check(self.lib.nrf_filter_mesh(self.h, C.c_uint64(int(min_triangles)), C.c_uint32(NRF_MESH_KEEP_LARGEST if keep_largest else 0),
+                                        C.c_void_p(stream or 0), C.byref(out)))
+        self._mesh_counts = (int(out.n_vertices), int(out.n_triangles))
+        self._mesh_parts_counts = (0, 0)
+        return out
 
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
