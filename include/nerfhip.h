@@ -689,6 +689,51 @@ enum { NRF_MESH_KEEP_LARGEST = 1 };  /* nrf_filter_mesh flags */
 int nrf_mesh_components(nrf_context* ctx, void* stream, nrf_mesh_parts* out);
 int nrf_read_mesh_components(nrf_context* ctx, uint32_t* labels, uint32_t* components);
 int nrf_filter_mesh(nrf_context* ctx, uint64_t min_triangles, uint32_t flags, void* stream, nrf_mesh* out);
+/* (ABI 7, addition) Mesh refinement: nrf_extract_mesh places a vertex by LINEAR interpolation of sigma between two lattice points, and
+ * sigma -- the exponential of a network output -- changes by large factors across one cell, so every vertex sits towards the outside
+ * lattice point (the terraces of a NeRF mesh).  A crossing edge has one endpoint inside and one outside: it brackets the iso value, and
+ * bisection along it converges whatever the density does in between.  nrf_refine_mesh does that on the device, in one launch with
+ * n_steps + 2 passes of the density network per vertex, between the extraction (or the filter) and the attributes:
+ *   edge word  nrf_extract_mesh records for every vertex w = (p << 3) | m: the lattice point p (< 2^27) that owns its edge and the edge
+ *              m = 1 .. 7; nrf_filter_mesh carries the words with the vertices it keeps.  xp = the position of p, xq = the position of
+ *              the point edge m runs to (origin + (float)index * cell, as above), e_c = xq_c - xp_c, and
+ *              point(u)_c = xp_c + u * e_c (the product rounded, then the sum: the form of the extraction's vertex).
+ *   s(x)       nrf_density at x, bit for bit: 0 where a coordinate is outside [-bound, bound] or not finite.
+ *   ends       s0 = s(xp), s1 = s(xq); in0 = s0 >= iso, in1 = s1 >= iso, with the lattice and the iso of the last nrf_extract_mesh.
+ *              in0 == in1: the vertex is UNBRACKETED -- it keeps its bits and its bracket record is (0, 1, s0, s1).  This happens only
+ *              where a caller's lattice disagrees with the network, or with NaN.
+ *   bisect     lo = 0, hi = 1, slo = s0, shi = s1; n_steps times: um = 0.5f * (lo + hi), sm = s(point(um)); if (sm >= iso) == in0 then
+ *              (lo, slo) = (um, sm), else (hi, shi) = (um, sm).
+ *   finish     one secant step in the final bracket: d = shi - slo; r = (iso - slo) / d; if (!(r >= 0 && r <= 1)) r = 0.5;
+ *              u = lo + r * (hi - lo); the vertex becomes point(u) and its bracket record (lo, hi, slo, shi).  Every operation is one
+ *              fp32 rounding.  (csrc/nrf_refine_plan.h is this text as code.)
+ *   With n_steps == 0 this is the extraction's interpolation on the network's own sigmas: a mesh extracted from the context's own
+ *   lattice (sigma_f32 == NULL) is left bit for bit as it was.  hi - lo == 2^-n_steps for every bracketed vertex.
+ * nrf_refine_mesh: the vertices of the context's current mesh are rewritten in place; the result depends on the edge words and not on
+ *   the current positions, so calling it twice with the same n_steps gives the same bits.  The buffers are owned by the context, grow
+ *   as needed and stay valid until the next nrf_extract_mesh, nrf_filter_mesh, nrf_refine_mesh or nrf_destroy.  Triangles, and a current
+ *   labelling of nrf_mesh_components, stay valid: topology does not change.  The attributes of the mesh are invalidated:
+ *   nrf_read_mesh_attributes returns NRF_E_STATE until nrf_mesh_attributes is asked again -- extract, filter, refine, attributes is the
+ *   cheap order.  An empty mesh is NRF_OK with zero counts.
+ * nrf_read_mesh_refinement: host copies of the current mesh's edge words (uint32 [n_vertices], readable after any extraction or
+ *   filter) and of the last refinement's bracket records (float [n_vertices][4], readable only after a refinement of the current
+ *   mesh); either may be NULL.
+ * The work is enqueued on `stream` (NULL: the context's) and nrf_refine_mesh returns after it has completed, as nrf_extract_mesh does:
+ * n_unbracketed has to reach the host.  NRF_E_INVALID: a NULL out; n_steps > 16 (the midpoints are exact up to there).  NRF_E_STATE: no
+ * model loaded (also for a mesh made from a caller's lattice on a context without a model); no mesh extracted yet;
+ * nrf_read_mesh_refinement with a brackets pointer: no refinement of the current mesh.  A refused call writes nothing.  The calls take
+ * no slot of the 16 calls in flight, leave nrf_get_stats untouched and write none of the context's frame buffers. */
+typedef struct nrf_mesh_refine {
+  uint64_t n_vertices;
+  uint64_t n_unbracketed; /* vertices left as they were (in0 == in1) */
+  void* vertices;         /* the mesh's vertex buffer, refined in place */
+  void* edges;            /* device uint32 [n_vertices] = (p << 3) | m */
+  void* brackets;         /* device float4 [n_vertices] = (lo, hi, s_lo, s_hi) */
+  uint32_t n_steps;
+  uint32_t reserved;      /* written as 0 */
+} nrf_mesh_refine;
+int nrf_refine_mesh(nrf_context* ctx, uint32_t n_steps, void* stream, nrf_mesh_refine* out);
+int nrf_read_mesh_refinement(nrf_context* ctx, uint32_t* edges, float* brackets_f32x4);
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

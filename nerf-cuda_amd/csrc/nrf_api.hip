@@ -24,6 +24,7 @@
 #include "nrf_grid_plan.h"
 #include "nrf_launch.h"
 #include "nrf_meshcc_plan.h"
+#include "nrf_refine_plan.h"
 #include "nrf_model_plan.h"
 #include "nrf_points_plan.h"
 
@@ -158,7 +159,7 @@ struct nrf_context {
   struct MeshBuffers {
     void *sigma = nullptr, *codes = nullptr, *vbase = nullptr, *tbase = nullptr, *partials = nullptr, *vertices = nullptr, *triangles = nullptr;
     size_t cap_sigma = 0, cap_codes = 0, cap_vbase = 0, cap_tbase = 0, cap_partials = 0, cap_vertices = 0, cap_triangles = 0;
-    uint32_t* totals = nullptr;  // device: n_vertices, n_triangles, the emit pass's flag, 0
+    uint32_t* totals = nullptr;  // device: n_vertices, n_triangles, the emit pass's flag, nrf_refine_mesh's count of unbracketed vertices
     uint64_t n_vertices = 0, n_triangles = 0;
     bool have = false;
     // nrf_mesh_attributes: float4 [n_vertices] each, of the mesh above (have_attr falls with every nrf_extract_mesh)
@@ -175,6 +176,14 @@ struct nrf_context {
     uint32_t n_rounds = 0;
     bool have_parts = false;
     void* sigma_used = nullptr;  // nrf_mesh.sigma of the extraction
+    // nrf_refine_mesh: the edge word of every vertex of the mesh above (written by nrf_extract_mesh, carried by nrf_filter_mesh into
+    // edges2, which is then swapped in), the lattice and the iso of the extraction, and the bracket records of the last refinement
+    // (have_brackets falls with every nrf_extract_mesh and nrf_filter_mesh)
+    void *edges = nullptr, *edges2 = nullptr, *brackets = nullptr;
+    size_t cap_edges = 0, cap_edges2 = 0, cap_brackets = 0;
+    MeshLattice lattice{};
+    float iso = 0.f;
+    bool have_brackets = false;
   } mesh;
 };
 
@@ -237,7 +246,7 @@ void free_frame(nrf_context* c) {
 void free_mesh(nrf_context* c) {
   auto& m = c->mesh;
   for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, m.normals, m.colors, (void*)m.totals,
-                  m.labels, m.rows, m.components, m.vertices2, m.triangles2, (void*)m.cc_words})
+                  m.labels, m.rows, m.components, m.vertices2, m.triangles2, (void*)m.cc_words, m.edges, m.edges2, m.brackets})
     if (q) (void)hipFree(q);
   m = nrf_context::MeshBuffers{};
 }
@@ -1853,6 +1862,7 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   m.have = false;
   m.have_attr = false;
   m.have_parts = false;
+  m.have_brackets = false;
   const uint64_t n = mesh_points(L);
   if ((rc = grow_mesh_buffer(&m.codes, m.cap_codes, n * 4))) return rc;
   if ((rc = grow_mesh_buffer(&m.vbase, m.cap_vbase, n * 4))) return rc;
@@ -1876,6 +1886,9 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   if ((rc = grow_mesh_buffer(&m.triangles, m.cap_triangles, mesh_triangle_bytes(nt)))) return rc;
   HIP_TRY(launch_mesh_emit(L, s, iso, (const uint32_t*)m.codes, (const uint32_t*)m.vbase, (const uint32_t*)m.tbase, nv, nt, (float*)m.vertices,
                            (uint32_t*)m.triangles, m.totals + 2, st));
+  // the edge words, while codes and vbase are the extraction's (nrf_mesh_components reuses them)
+  if ((rc = grow_mesh_buffer(&m.edges, m.cap_edges, refine_edge_bytes(nv)))) return rc;
+  HIP_TRY(launch_mesh_edges(L, (const uint32_t*)m.codes, (const uint32_t*)m.vbase, nv, (uint32_t*)m.edges, m.totals + 2, st));
   HIP_TRY(hipMemcpyAsync(host, m.totals, 16, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (host[2]) return fail(NRF_E_HIP, "nrf_extract_mesh: the count and the emit pass disagree (the sigmas changed during the call); writes were dropped");
@@ -1883,6 +1896,8 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   m.n_triangles = nt;
   m.have = true;
   m.sigma_used = const_cast<float*>(s);
+  m.lattice = L;
+  m.iso = iso;
   out->n_vertices = nv;
   out->n_triangles = nt;
   out->vertices = nv ? m.vertices : nullptr;
@@ -2041,9 +2056,11 @@ int nrf_filter_mesh(nrf_context* c, uint64_t min_triangles, uint32_t flags, void
     if (kept[0] > nv || kept[1] > nt) return fail(NRF_E_HIP, "nrf_filter_mesh: the kept counts exceed the mesh");
     if ((rc = grow_mesh_buffer(&m.vertices2, m.cap_vertices2, mesh_vertex_bytes(kept[0])))) return rc;
     if ((rc = grow_mesh_buffer(&m.triangles2, m.cap_triangles2, mesh_triangle_bytes(kept[1])))) return rc;
+    if ((rc = grow_mesh_buffer(&m.edges2, m.cap_edges2, refine_edge_bytes(kept[0])))) return rc;
     uint32_t dropped = 0;
     HIP_TRY(launch_meshcc_scatter(A, (const float*)m.vertices, (const uint32_t*)m.codes, (const uint32_t*)m.vbase, (const uint32_t*)m.tbase, kept[0],
-                                  kept[1], (float*)m.vertices2, (uint32_t*)m.triangles2, m.cc_words + 3, st));
+                                  kept[1], (float*)m.vertices2, (uint32_t*)m.triangles2, m.cc_words + 3, st, (const uint32_t*)m.edges,
+                                  kept[0] ? (uint32_t*)m.edges2 : nullptr));
     HIP_TRY(hipMemcpyAsync(&dropped, m.cc_words + 3, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (dropped) return fail(NRF_E_HIP, "nrf_filter_mesh: the scan and the scatter pass disagree (the mesh changed during the call); writes were dropped");
@@ -2051,11 +2068,14 @@ int nrf_filter_mesh(nrf_context* c, uint64_t min_triangles, uint32_t flags, void
     std::swap(m.cap_vertices, m.cap_vertices2);
     std::swap(m.triangles, m.triangles2);
     std::swap(m.cap_triangles, m.cap_triangles2);
+    std::swap(m.edges, m.edges2);
+    std::swap(m.cap_edges, m.cap_edges2);
     m.n_vertices = kept[0];
     m.n_triangles = kept[1];
   }
   m.have_parts = false;
   m.have_attr = false;
+  m.have_brackets = false;
   out->n_vertices = m.n_vertices;
   out->n_triangles = m.n_triangles;
   out->vertices = m.n_vertices ? m.vertices : nullptr;
@@ -2118,6 +2138,60 @@ int nrf_read_mesh_attributes(nrf_context* c, float* normals, float* colors) {
   const auto& m = c->mesh;
   if (normals && m.n_vertices) HIP_TRY(hipMemcpy(normals, m.normals, (size_t)m.n_vertices * 16, hipMemcpyDeviceToHost));
   if (colors && m.n_vertices) HIP_TRY(hipMemcpy(colors, m.colors, (size_t)m.n_vertices * 16, hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// Mesh refinement (nrf_kernels_refine.hip; the definition is nrf_refine_plan.h's).  Like the extraction: no slot of the 16-call ring,
+// no statistics, no frame buffer; it returns after completion, because the count of unbracketed vertices has to reach the host.
+int nrf_refine_mesh(nrf_context* c, uint32_t n_steps, void* stream, nrf_mesh_refine* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (!refine_steps_valid(n_steps)) return fail(NRF_E_INVALID, "nrf_refine_mesh: n_steps must be 0 .. 16");
+  STAGE_PROLOGUE();  // (a mesh made from a caller's lattice on a context without a model has no network to ask: NRF_E_STATE)
+  auto& m = c->mesh;
+  if (!m.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  m.have_brackets = false;
+  m.have_attr = false;
+  const uint64_t nv = m.n_vertices;
+  uint32_t open = 0;
+  if (nv) {
+    if ((rc = grow_mesh_buffer(&m.brackets, m.cap_brackets, refine_bracket_bytes(nv)))) return rc;
+    RefineArgs A;
+    A.L = m.lattice;
+    A.iso = m.iso;
+    A.bound = c->desc.bound;
+    A.n = (uint32_t)nv;
+    A.n_steps = n_steps;
+    A.edges = (const uint32_t*)m.edges;
+    A.vertices = (float*)m.vertices;
+    A.brackets = (float*)m.brackets;
+    A.n_unbracketed = m.totals + 3;
+    HIP_TRY(hipMemsetAsync(m.totals + 3, 0, 4, st));
+    HIP_TRY(launch_refine(c->dm, A, st));
+    HIP_TRY(hipMemcpyAsync(&open, m.totals + 3, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  m.have_brackets = true;
+  out->n_vertices = nv;
+  out->n_unbracketed = open;
+  out->vertices = nv ? m.vertices : nullptr;
+  out->edges = nv ? m.edges : nullptr;
+  out->brackets = nv ? m.brackets : nullptr;
+  out->n_steps = n_steps;
+  out->reserved = 0;
+  return NRF_OK;
+}
+
+int nrf_read_mesh_refinement(nrf_context* c, uint32_t* edges, float* brackets) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!c->mesh.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  if (brackets && !c->mesh.have_brackets)
+    return fail(NRF_E_STATE, "no brackets of the current mesh (call nrf_refine_mesh after nrf_extract_mesh or nrf_filter_mesh)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const auto& m = c->mesh;
+  if (edges && m.n_vertices) HIP_TRY(hipMemcpy(edges, m.edges, (size_t)refine_edge_bytes(m.n_vertices), hipMemcpyDeviceToHost));
+  if (brackets && m.n_vertices) HIP_TRY(hipMemcpy(brackets, m.brackets, (size_t)refine_bracket_bytes(m.n_vertices), hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

@@ -7,10 +7,12 @@
 //                              (launch_mesh_scan: also the scan of nrf_kernels_meshcc.hip, over code words that decode to 0 / 1)
 //   mesh_emit_kernel           the vertices and the triangles at their scanned offsets; every write is checked against the element
 //                              counts the buffers hold, a write that would fall outside is dropped and raises *flag
+//   mesh_edges_kernel          the edge word (p << 3) | m of every vertex, for nrf_refine_mesh; checked and flagged like emit's writes
 // Streaming kernels: a lattice point reads its cell's eight sigmas (count, emit) and, where its cell has triangles, the codes and
 // vertex bases of the corners that own its edges -- neighbours in the lattice, served by L2.  The triangle table is indexed by
 // run-time values and lives in constant memory; nothing here has a private array that is.
 #include "nrf_launch.h"
+#include "nrf_refine_plan.h"
 
 namespace nrf {
 
@@ -128,6 +130,16 @@ __global__ __launch_bounds__(256) void mesh_emit_kernel(const MeshLattice L, con
   }
 }
 
+// the edge word of every vertex, in emit's numbering (nrf_refine_plan.h); every write is checked against n_vertices, as emit's are
+__global__ __launch_bounds__(256) void mesh_edges_kernel(uint32_t n, const uint32_t* __restrict__ codes, const uint32_t* __restrict__ vbase,
+                                                         uint32_t n_vertices, uint32_t* __restrict__ edges, uint32_t* flag) {
+  for (uint32_t p = blockIdx.x * MESH_BLOCK + threadIdx.x; p < n; p += gridDim.x * MESH_BLOCK) {
+    const uint32_t code = codes[p];
+    if (!(code & 0xfeu)) continue;
+    if (!refine_emit_edges(p, code, vbase[p], n_vertices, edges)) *flag = 1u;
+  }
+}
+
 // grid-stride launches: at most 2048 workgroups of 256 lanes
 constexpr uint32_t MESH_MAX_GROUPS = 2048;
 static uint32_t mesh_groups(uint32_t n) {
@@ -162,6 +174,15 @@ hipError_t launch_mesh_emit(const MeshLattice& L, const float* sigma, float iso,
   const uint32_t n = mesh_points(L);
   hipLaunchKernelGGL(mesh_emit_kernel, dim3(mesh_groups(n)), dim3(MESH_BLOCK), 0, st, L, sigma, iso, n, codes, vbase, tbase, n_vertices,
                      n_triangles, vertices, triangles, flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_mesh_edges(const MeshLattice& L, const uint32_t* codes, const uint32_t* vbase, uint32_t n_vertices, uint32_t* edges,
+                             uint32_t* flag, hipStream_t st) {
+  if (!mesh_lattice_valid(L.origin, L.cell, L.dims) || !codes || !vbase || !flag || (n_vertices && !edges)) return hipErrorInvalidValue;
+  if (!n_vertices) return hipSuccess;
+  const uint32_t n = mesh_points(L);
+  hipLaunchKernelGGL(mesh_edges_kernel, dim3(mesh_groups(n)), dim3(MESH_BLOCK), 0, st, n, codes, vbase, n_vertices, edges, flag);
   return hipGetLastError();
 }
 

@@ -9,7 +9,8 @@
 //   meshcc_table_{vertices,triangles}_kernel   the table's labels and counts, integer atomicAdd; meshcc_best_kernel: one 64-bit atomicMax per row
 //   meshcc_keep_kernel                     keep flags of vertex i and triangle i as one scan code word
 //   meshcc_scatter_kernel                  kept vertices and remapped kept triangles into SECOND buffers (in place, a lane would overwrite
-//                                          what another lane has yet to read); every write is checked against the counted sizes
+//                                          what another lane has yet to read); every write is checked against the counted sizes; a kept
+//                                          vertex's edge word (nrf_refine_plan.h) travels with it into a second buffer of its own
 //
 // Why no launch here waits for, or needs to see, what another workgroup writes during it.  The labelling is a loop of launches on the
 // host (nrf_api.hip), and within a launch only this invariant is relied on:
@@ -145,12 +146,18 @@ __global__ __launch_bounds__(256) void meshcc_scatter_kernel(const uint32_t* __r
                                                              uint32_t n_vertices, uint32_t n_triangles, const uint32_t* __restrict__ codes,
                                                              const uint32_t* __restrict__ vnew, const uint32_t* __restrict__ tnew,
                                                              uint32_t kept_vertices, uint32_t kept_triangles, uint32_t* __restrict__ vertices_out,
-                                                             uint32_t* __restrict__ triangles_out, uint32_t* flag) {
+                                                             uint32_t* __restrict__ triangles_out, uint32_t* flag,
+                                                             const uint32_t* __restrict__ edges, uint32_t* __restrict__ edges_out) {
   const uint32_t n = n_vertices > n_triangles ? n_vertices : n_triangles;
   bool ok = true;
   MESHCC_FOR(i, n) {
     const uint32_t code = codes[i];
-    if (i < n_vertices && (code & 2u)) ok = meshcc_move_vertex(vertices, i, vnew[i], kept_vertices, vertices_out) && ok;
+    if (i < n_vertices && (code & 2u)) {
+      const uint32_t to = vnew[i];
+      const bool moved = meshcc_move_vertex(vertices, i, to, kept_vertices, vertices_out);
+      if (moved && edges) edges_out[to] = edges[i];  // (moved: to < kept_vertices, the elements edges_out holds)
+      ok = moved && ok;
+    }
     if (i < n_triangles && (code & 0x100u))
       ok = meshcc_move_triangle(triangles, i, tnew[i], codes, vnew, n_vertices, kept_vertices, kept_triangles, triangles_out) && ok;
   }
@@ -201,15 +208,17 @@ hipError_t launch_meshcc_keep(const MeshccArgs& A, uint64_t min_triangles, uint3
 
 hipError_t launch_meshcc_scatter(const MeshccArgs& A, const float* vertices, const uint32_t* codes, const uint32_t* vnew, const uint32_t* tnew,
                                  uint32_t kept_vertices, uint32_t kept_triangles, float* vertices_out, uint32_t* triangles_out, uint32_t* flag,
-                                 hipStream_t st) {
+                                 hipStream_t st, const uint32_t* edges, uint32_t* edges_out) {
   if (!meshcc_args_valid(A) || !vertices || !codes || !vnew || !tnew || !flag) return hipErrorInvalidValue;
+  if ((edges != nullptr) != (edges_out != nullptr) && kept_vertices) return hipErrorInvalidValue;
+  if (!edges_out) edges = nullptr;
   if ((kept_vertices && !vertices_out) || (kept_triangles && !triangles_out)) return hipErrorInvalidValue;
   if (kept_vertices > A.n_vertices || kept_triangles > A.n_triangles) return hipErrorInvalidValue;
   if (!kept_vertices && !kept_triangles) return hipSuccess;
   const uint32_t n = A.n_vertices > A.n_triangles ? A.n_vertices : A.n_triangles;
   hipLaunchKernelGGL(meshcc_scatter_kernel, dim3(meshcc_groups(n)), dim3(MESHCC_BLOCK), 0, st, reinterpret_cast<const uint32_t*>(vertices), A.triangles,
                      A.n_vertices, A.n_triangles, codes, vnew, tnew, kept_vertices, kept_triangles, reinterpret_cast<uint32_t*>(vertices_out),
-                     triangles_out, flag);
+                     triangles_out, flag, edges, edges_out);
   return hipGetLastError();
 }
 

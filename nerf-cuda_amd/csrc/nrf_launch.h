@@ -119,6 +119,23 @@ hipError_t launch_mesh_emit(const MeshLattice& L, const float* sigma, float iso,
 //                      sums of mesh_code_vertices / mesh_code_triangles of the codes, totals[0 .. 1] = the sums
 hipError_t launch_mesh_scan(const uint32_t* codes, uint32_t n, uint32_t* vbase, uint32_t* tbase, void* partials, uint32_t* totals,
                             hipStream_t st);
+//   launch_mesh_edges  edges [n_vertices] = the edge word (p << 3) | m of every vertex (nrf_refine_plan.h), from the codes and vbase of
+//                      launch_mesh_count while they are valid; *flag as launch_mesh_emit has it
+hipError_t launch_mesh_edges(const MeshLattice& L, const uint32_t* codes, const uint32_t* vbase, uint32_t n_vertices, uint32_t* edges,
+                             uint32_t* flag, hipStream_t st);
+// Mesh refinement (nrf_kernels_refine.hip, arithmetic: nrf_refine_plan.h): every vertex moves along the lattice edge its edge word names
+// onto the iso value of the density network, n_steps bisections and a secant step, n_steps + 2 network passes per chunk in one launch.
+// Launch sizes and LDS are launch_points' for the model's stage instance.
+struct RefineArgs {
+  MeshLattice L;                      // the lattice and the iso of the extraction
+  float iso = 0.f, bound = 0.f;
+  uint32_t n = 0, n_steps = 0;
+  const uint32_t* edges = nullptr;    // [n]
+  float* vertices = nullptr;          // [n][3], rewritten in place where the edge brackets iso
+  float* brackets = nullptr;          // [n][4] = (lo, hi, s_lo, s_hi)
+  uint32_t* n_unbracketed = nullptr;  // += the vertices left as they were (zeroed by the caller)
+};
+hipError_t launch_refine(const DevModel& M, const RefineArgs& A, hipStream_t st);
 // Connected components and the filter by component size of an indexed mesh (nrf_kernels_meshcc.hip, definition: nrf_meshcc_plan.h);
 // n_vertices > 0.  Every launch is a streaming pass that needs nothing another workgroup writes during it.
 //   launch_meshcc_init      parent[v] = v
@@ -128,7 +145,8 @@ hipError_t launch_mesh_scan(const uint32_t* codes, uint32_t n, uint32_t* vbase, 
 //                           then *best = the maximum of meshcc_key over the rows (zeroed by the caller)
 //   launch_meshcc_keep      codes[i], i < max(n_vertices, n_triangles): the keep flags of vertex i and triangle i as a scan code word
 //   launch_meshcc_scatter   the kept vertices and the remapped kept triangles into second buffers of kept_vertices / kept_triangles
-//                           elements; *flag is set to 1 when a write was dropped because it would have fallen outside those counts
+//                           elements; *flag is set to 1 when a write was dropped because it would have fallen outside those counts.
+//                           edges / edges_out (both or neither): the kept vertices' edge words travel with them (nrf_refine_plan.h)
 struct MeshccArgs {
   uint32_t n_vertices = 0, n_triangles = 0;
   const uint32_t* triangles = nullptr;  // [n_triangles][3]
@@ -145,7 +163,7 @@ hipError_t launch_meshcc_table(const MeshccArgs& A, hipStream_t st);
 hipError_t launch_meshcc_keep(const MeshccArgs& A, uint64_t min_triangles, uint32_t flags, uint32_t* codes, hipStream_t st);
 hipError_t launch_meshcc_scatter(const MeshccArgs& A, const float* vertices, const uint32_t* codes, const uint32_t* vnew, const uint32_t* tnew,
                                  uint32_t kept_vertices, uint32_t kept_triangles, float* vertices_out, uint32_t* triangles_out, uint32_t* flag,
-                                 hipStream_t st);
+                                 hipStream_t st, const uint32_t* edges = nullptr, uint32_t* edges_out = nullptr);
 hipError_t launch_density_positions(uint32_t H, float k, void* xyz, void* dir, hipStream_t st);
 hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int n_iterations, void* grid, hipStream_t st);
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,

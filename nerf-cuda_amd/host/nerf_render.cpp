@@ -652,6 +652,19 @@ NerfRender::Mesh NerfRender::filter_mesh(uint64_t min_triangles, bool keep_large
   return out;
 }
 
+NerfRender::MeshRefinement NerfRender::refine_mesh(uint32_t n_steps) {
+  if (!m_have_network) throw std::runtime_error{"refine_mesh: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"refine_mesh: single-device renderers only"};
+  nrf_mesh_refine r{};
+  check(nrf_refine_mesh(m_ctx[0], n_steps, nullptr, &r), "nrf_refine_mesh");
+  MeshRefinement out;
+  out.vertices.resize(3 * (size_t)r.n_vertices);
+  check(nrf_read_mesh(m_ctx[0], out.vertices.data(), nullptr), "nrf_read_mesh");
+  out.unbracketed = r.n_unbracketed;
+  out.vertices_dev = r.vertices;
+  return out;
+}
+
 bool NerfRender::save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
                           const std::vector<float>& normals) {
   std::FILE* f = std::fopen(path.c_str(), "w");

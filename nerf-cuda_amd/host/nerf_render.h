@@ -127,6 +127,16 @@ class NerfRender {
   // most triangles, a tie going to the smaller label -- and makes the result the context's mesh (mesh_attributes then sees it) -> the
   // filtered mesh as extract_mesh returns one.  Synchronous; single device.
   Mesh filter_mesh(uint64_t min_triangles, bool keep_largest);
+  // nrf_refine_mesh (nerfhip.h): every vertex of the context's mesh moves along its lattice edge onto the iso value of the density
+  // network, n_steps (0 .. 16) bisections and one secant step, in one launch on the device -> the refined host vertices [n][3] (the
+  // triangles do not change; vertices_dev is the same buffer, rewritten in place) and the number of vertices left as they were because
+  // their edge does not bracket iso.  After filter_mesh and before mesh_attributes is the cheap order.  Synchronous; single device.
+  struct MeshRefinement {
+    std::vector<float> vertices;
+    uint64_t unbracketed = 0;
+    const void* vertices_dev = nullptr;
+  };
+  MeshRefinement refine_mesh(uint32_t n_steps);
   // Wavefront OBJ: "v x y z" per vertex, "vn x y z" per vertex when normals ([n][3]) has one per vertex, faces 1-based ("f a//a b//b c//c"
   // with normals, "f a b c" without).  Returns false when the file cannot be written.
   static bool save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,

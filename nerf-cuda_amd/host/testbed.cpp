@@ -10,6 +10,8 @@
 //   [--mesh_min_triangles N] [--mesh_largest] -- between extraction and attributes the mesh is filtered on the device by connected
 //   component (NerfRender::mesh_components, filter_mesh): components with fewer than N triangles are dropped, --mesh_largest keeps only
 //   the component with the most triangles
+//   [--mesh_refine N] -- after the filter and before the attributes every vertex is moved along its lattice edge onto the iso value of
+//   the density network, N (0 .. 16) bisections and a secant step on the device (NerfRender::refine_mesh)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -33,13 +35,15 @@ int main(int argc, char** argv) {
   float mesh_iso = 2.5f;  // (instant-ngp's default mesh threshold)
   unsigned long long mesh_min_triangles = 0;
   bool mesh_largest = false;
+  int mesh_refine = -1;  // (off)
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
-      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles") && i + 1 < argc) {
+      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine") && i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
         else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
+        else if (a == "--mesh_refine") mesh_refine = std::atoi(argv[++i]);
         else if (a == "--mesh_min_triangles") mesh_min_triangles = std::strtoull(argv[++i], nullptr, 10);
         else mesh_iso = (float)std::atof(argv[++i]);
       } else if (a == "--mesh_largest") {
@@ -139,6 +143,16 @@ int main(int argc, char** argv) {
         for (size_t r = 0; r < rows; ++r) kept += parts.table[3 * r + 2] >= mesh_min_triangles && (!mesh_largest || r == largest);
         std::printf("mesh filter: %zu components, %zu kept, vertices %zu -> %zu, triangles %zu -> %zu, %f s\n", rows, kept, nv0,
                     mesh.vertices.size() / 3, nt0, mesh.triangles.size() / 3, std::chrono::duration<double>(f1 - f0).count());
+      }
+      if (mesh_refine >= 0) {
+        // onto the iso-surface, on the device, after the filter (fewer vertices) and before the attributes (they are taken at the positions)
+        const auto r0 = std::chrono::steady_clock::now();
+        NerfRender::MeshRefinement refined = render->refine_mesh((uint32_t)mesh_refine);
+        const auto r1 = std::chrono::steady_clock::now();
+        std::printf("mesh refine: %d steps, %zu vertices, %llu unbracketed, %f s\n", mesh_refine, refined.vertices.size() / 3,
+                    (unsigned long long)refined.unbracketed, std::chrono::duration<double>(r1 - r0).count());
+        mesh.vertices = std::move(refined.vertices);
+        mesh.vertices_dev = refined.vertices_dev;
       }
       if (mesh_path.size() >= 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0) {
         // normals and colours in one launch at the device vertices (a vertex within the step of the box's faces gets zeros)

@@ -193,6 +193,19 @@ class MeshParts(C.Structure):
 NRF_MESH_KEEP_LARGEST = 1
 
 
+class MeshRefine(C.Structure):
+    """nrf_mesh_refine: device pointers owned by the context, valid until the next extract_mesh, filter_mesh, refine_mesh or close."""
+    _fields_ = [
+        ("n_vertices", C.c_uint64),
+        ("n_unbracketed", C.c_uint64),  # vertices left as they were
+        ("vertices", C.c_void_p),       # float [n_vertices][3]: the mesh's vertex buffer, refined in place
+        ("edges", C.c_void_p),          # uint32 [n_vertices] = (p << 3) | m
+        ("brackets", C.c_void_p),       # float4 [n_vertices] = (lo, hi, s_lo, s_hi)
+        ("n_steps", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64),
@@ -321,6 +334,8 @@ _SIGS = {
     "nrf_mesh_components": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(MeshParts)]),
     "nrf_read_mesh_components": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "nrf_filter_mesh": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(Mesh)]),
+    "nrf_refine_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MeshRefine)]),
+    "nrf_read_mesh_refinement": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -951,6 +966,26 @@ class NerfHip:
         self._mesh_counts = (int(out.n_vertices), int(out.n_triangles))
         self._mesh_parts_counts = (0, 0)
         return out
+
+    def refine_mesh(self, n_steps: int, stream=None) -> MeshRefine:
+        """nrf_refine_mesh: moves every vertex of the current mesh along its lattice edge onto the iso value of the density network --
+        n_steps (0 .. 16) bisections and one secant step, in one launch -- and rewrites the vertices in place.  Triangles and a current
+        labelling stay valid; the attributes are invalid afterwards.  Returns after completion; out.n_unbracketed counts the vertices
+        whose edge does not bracket iso (a caller's lattice that disagrees with the network): they keep their bits."""
+        out = MeshRefine()
+        _check(self.lib.nrf_refine_mesh(self.h, C.c_uint32(int(n_steps)), C.c_void_p(stream or 0), C.byref(out)))
+        return out
+
+    def read_mesh_refinement(self, brackets: bool = True):
+        """nrf_read_mesh_refinement: (edges uint32 [n_vertices] = (p << 3) | m, brackets float32 [n_vertices][4] = (lo, hi, s_lo, s_hi))
+        of the current mesh.  The edge words exist after any extract_mesh or filter_mesh; the brackets only after a refine_mesh of the
+        current mesh -- brackets=False reads the edge words alone and returns (edges, None)."""
+        nv = getattr(self, "_mesh_counts", (0, 0))[0]
+        e = np.empty(nv, np.uint32)
+        b = np.empty((nv, 4), np.float32) if brackets else None
+        _check(self.lib.nrf_read_mesh_refinement(self.h, e.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 b.ctypes.data_as(C.POINTER(C.c_float)) if brackets else None))
+        return e, b
 
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
