@@ -734,6 +734,57 @@ typedef struct nrf_mesh_refine {
 } nrf_mesh_refine;
 int nrf_refine_mesh(nrf_context* ctx, uint32_t n_steps, void* stream, nrf_mesh_refine* out);
 int nrf_read_mesh_refinement(nrf_context* ctx, uint32_t* edges, float* brackets_f32x4);
+/* (ABI 7, addition) Mesh simplification: marching tetrahedra emits about twice the triangles of the cube table, many of them slivers,
+ * and a collision proxy, a shadow caster or a preview mesh has a triangle budget.  A coarser lattice loses exactly the thin parts the
+ * refinement was written to place, so nrf_simplify_mesh decimates the context's current mesh where it lives, by vertex clustering on
+ * the lattice of the last nrf_extract_mesh.  Its representatives are vertices of the mesh itself, so every vertex of the result is an
+ * old vertex with its float bits and its edge word -- still on the iso-surface after a refinement, and nrf_refine_mesh afterwards still
+ * works.  No model is needed.  Integers and copied float bits, but for the nine fp32 operations of the key:
+ *   cluster    the owner point of vertex v is p = word >> 3 = (i * ny + j) * nz + k of its edge word (above).  Its block is
+ *              b_c = index_c / factor (integer division) of nb_c = (dims_c - 1) / factor + 1 blocks per axis, and its cluster
+ *              cid = (b_x * nb_y + b_y) * nb_z + b_z.  factor = 1 .. 256; factor 1 already merges the up to seven vertices one point owns.
+ *   key        the block's centre cc_c = origin_c + (float)((2 * b_c + 1) * factor) * (0.5f * cell_c) (the integer converted to fp32, the
+ *              half cell, the product, the sum: one rounding each); d_c = v_c - cc_c with v the vertex's CURRENT position;
+ *              d2 = (d_x * d_x + d_y * d_y) + d_z * d_z, three products and two sums in this order, one rounding each;
+ *              hi = d2 < +inf ? bits(d2) : 0x7f800000 (NaN and inf rank last; d2 >= +0, so the bits order as the values do);
+ *              key = (uint64)hi << 32 | v.
+ *   rep        rep(v) = the low word of the minimum key over the vertices of v's cluster: the vertex nearest its block's centre, a tie
+ *              going to the smaller id.  A minimum does not depend on the order in which anything ran.
+ *   triangles  (a, b, c) maps to (rep a, rep b, rep c) in that order and survives iff the three are pairwise different; a triangle that
+ *              names a vertex >= n_vertices is dropped.  Survivors keep their relative order.  Duplicate and mutually opposite
+ *              triangles are KEPT, on purpose: the vertex map commutes with the boundary operator, so a closed mesh stays closed as a
+ *              chain -- every directed edge occurs as often as its opposite -- and its signed volume keeps a meaning.
+ *   vertices   a vertex is kept iff it is a representative and a surviving triangle names it.  Its new id is the number of kept
+ *              vertices with a smaller old id; its float bits and its edge word are copied.  The result has no unreferenced vertex.
+ *   records    sources[new] = old id, ascending.  vertex_map[old v] = the new id of rep(v), or 0xffffffff where rep(v) was not kept.
+ *              (csrc/nrf_simplify_plan.h is this text as code.)
+ * nrf_simplify_mesh: the context's mesh BECOMES the simplified mesh, as with nrf_filter_mesh -- nrf_read_mesh, nrf_mesh_components,
+ *   nrf_filter_mesh, nrf_refine_mesh, nrf_mesh_attributes and nrf_read_mesh_refinement's edge words all see it; earlier vertices /
+ *   triangles / edges pointers are invalid.  It invalidates the labelling, the attributes and the bracket records of the mesh it
+ *   replaced: their read calls return NRF_E_STATE until asked again.  sources and vertex_map stay valid until the next nrf_extract_mesh,
+ *   nrf_filter_mesh, nrf_simplify_mesh or nrf_destroy.  An empty mesh, or a result with nothing left, is NRF_OK with zero counts.
+ *   Memory: a dense key table of 8 bytes per cluster -- 16 MB for a 256^3 lattice at factor 2, 128 MB at factor 1 -- and 4 bytes per
+ *   vertex and per triangle of flags, owned by the context and kept for the next call.
+ * nrf_read_mesh_simplification: host copies of the last simplification's records: uint32 [n_vertices] and uint32 [n_vertices_before];
+ *   either may be NULL.
+ * The work is enqueued on `stream` (NULL: the context's) and nrf_simplify_mesh returns after it has completed, as nrf_filter_mesh does:
+ * the sizes have to reach the host.  NRF_E_INVALID: a NULL out; factor 0 or > 256.  NRF_E_STATE: no mesh extracted yet;
+ * nrf_read_mesh_simplification: no simplification of the current mesh.  NRF_E_HIP with a message: a scatter write fell outside the
+ * counted sizes (every write is checked, as in the filter).  A refused call writes nothing.  The calls take no slot of the 16 calls in
+ * flight, leave nrf_get_stats untouched and write none of the context's frame buffers. */
+typedef struct nrf_mesh_simplify {
+  uint64_t n_vertices, n_triangles;               /* after */
+  uint64_t n_vertices_before, n_triangles_before;
+  void* vertices;    /* device float [n_vertices][3]: the context's mesh */
+  void* triangles;   /* device uint32 [n_triangles][3] */
+  void* edges;       /* device uint32 [n_vertices]: the kept vertices' edge words */
+  void* sources;     /* device uint32 [n_vertices] */
+  void* vertex_map;  /* device uint32 [n_vertices_before] */
+  uint32_t factor;
+  uint32_t reserved; /* written as 0 */
+} nrf_mesh_simplify;
+int nrf_simplify_mesh(nrf_context* ctx, uint32_t factor, void* stream, nrf_mesh_simplify* out);
+int nrf_read_mesh_simplification(nrf_context* ctx, uint32_t* sources, uint32_t* vertex_map);
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

@@ -25,6 +25,7 @@
 #include "nrf_launch.h"
 #include "nrf_meshcc_plan.h"
 #include "nrf_refine_plan.h"
+#include "nrf_simplify_plan.h"
 #include "nrf_model_plan.h"
 #include "nrf_points_plan.h"
 
@@ -167,7 +168,8 @@ struct nrf_context {
     size_t cap_normals = 0, cap_colors = 0;
     bool have_attr = false;
     // nrf_mesh_components / nrf_filter_mesh: the labelling and the table of the mesh above (have_parts falls with every
-    // nrf_extract_mesh and nrf_filter_mesh), the second vertex / triangle buffers the filter scatters into and then swaps in, and
+    // nrf_extract_mesh, nrf_filter_mesh and nrf_simplify_mesh), the second vertex / triangle buffers the filter scatters into and then
+    // swaps in, and
     // cc_words (device): the largest component's key (64 bits), the hook's changed flag, the scatter's flag, a scan's two totals
     void *labels = nullptr, *rows = nullptr, *components = nullptr, *vertices2 = nullptr, *triangles2 = nullptr;
     size_t cap_labels = 0, cap_rows = 0, cap_components = 0, cap_vertices2 = 0, cap_triangles2 = 0;
@@ -178,12 +180,19 @@ struct nrf_context {
     void* sigma_used = nullptr;  // nrf_mesh.sigma of the extraction
     // nrf_refine_mesh: the edge word of every vertex of the mesh above (written by nrf_extract_mesh, carried by nrf_filter_mesh into
     // edges2, which is then swapped in), the lattice and the iso of the extraction, and the bracket records of the last refinement
-    // (have_brackets falls with every nrf_extract_mesh and nrf_filter_mesh)
+    // (have_brackets falls with every nrf_extract_mesh, nrf_filter_mesh and nrf_simplify_mesh)
     void *edges = nullptr, *edges2 = nullptr, *brackets = nullptr;
     size_t cap_edges = 0, cap_edges2 = 0, cap_brackets = 0;
     MeshLattice lattice{};
     float iso = 0.f;
     bool have_brackets = false;
+    // nrf_simplify_mesh: the dense key table, the used / survive flags, and the records of the last simplification (have_simplify
+    // falls with every nrf_extract_mesh and nrf_filter_mesh); n_vertices_before = the elements of vertex_map; it scatters into
+    // vertices2 / triangles2 / edges2 and swaps them in, as the filter does
+    void *skeys = nullptr, *sused = nullptr, *ssurvive = nullptr, *sources = nullptr, *vertex_map = nullptr;
+    size_t cap_skeys = 0, cap_sused = 0, cap_ssurvive = 0, cap_sources = 0, cap_vertex_map = 0;
+    uint64_t n_vertices_before = 0;
+    bool have_simplify = false;
   } mesh;
 };
 
@@ -246,7 +255,8 @@ void free_frame(nrf_context* c) {
 void free_mesh(nrf_context* c) {
   auto& m = c->mesh;
   for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, m.normals, m.colors, (void*)m.totals,
-                  m.labels, m.rows, m.components, m.vertices2, m.triangles2, (void*)m.cc_words, m.edges, m.edges2, m.brackets})
+                  m.labels, m.rows, m.components, m.vertices2, m.triangles2, (void*)m.cc_words, m.edges, m.edges2, m.brackets,
+                  m.skeys, m.sused, m.ssurvive, m.sources, m.vertex_map})
     if (q) (void)hipFree(q);
   m = nrf_context::MeshBuffers{};
 }
@@ -1863,6 +1873,7 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   m.have_attr = false;
   m.have_parts = false;
   m.have_brackets = false;
+  m.have_simplify = false;
   const uint64_t n = mesh_points(L);
   if ((rc = grow_mesh_buffer(&m.codes, m.cap_codes, n * 4))) return rc;
   if ((rc = grow_mesh_buffer(&m.vbase, m.cap_vbase, n * 4))) return rc;
@@ -2076,6 +2087,7 @@ int nrf_filter_mesh(nrf_context* c, uint64_t min_triangles, uint32_t flags, void
   m.have_parts = false;
   m.have_attr = false;
   m.have_brackets = false;
+  m.have_simplify = false;
   out->n_vertices = m.n_vertices;
   out->n_triangles = m.n_triangles;
   out->vertices = m.n_vertices ? m.vertices : nullptr;
@@ -2192,6 +2204,99 @@ int nrf_read_mesh_refinement(nrf_context* c, uint32_t* edges, float* brackets) {
   const auto& m = c->mesh;
   if (edges && m.n_vertices) HIP_TRY(hipMemcpy(edges, m.edges, (size_t)refine_edge_bytes(m.n_vertices), hipMemcpyDeviceToHost));
   if (brackets && m.n_vertices) HIP_TRY(hipMemcpy(brackets, m.brackets, (size_t)refine_bracket_bytes(m.n_vertices), hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// Mesh simplification by vertex clustering (nrf_kernels_simplify.hip; the definition is nrf_simplify_plan.h's).  Like the filter: no
+// slot of the 16-call ring, no statistics, no frame buffer, and no model; it returns after completion, because the sizes have to
+// reach the host.
+int nrf_simplify_mesh(nrf_context* c, uint32_t factor, void* stream, nrf_mesh_simplify* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (!simplify_factor_valid(factor)) return fail(NRF_E_INVALID, "nrf_simplify_mesh: factor must be 1 .. 256");
+  auto& m = c->mesh;
+  if (!m.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const uint64_t nv = m.n_vertices, nt = m.n_triangles, n = nv > nt ? nv : nt;
+  uint32_t kept[2] = {0, 0};
+  m.have_simplify = false;
+  if (nv) {
+    SimplifyArgs A;
+    A.L = m.lattice;
+    A.factor = factor;
+    A.n_clusters = simplify_clusters(m.lattice, factor);
+    A.n_vertices = (uint32_t)nv;
+    A.n_triangles = (uint32_t)nt;
+    if ((rc = grow_mesh_scan(c, n))) return rc;
+    if ((rc = grow_mesh_buffer(&m.skeys, m.cap_skeys, simplify_key_bytes(A.n_clusters)))) return rc;
+    if ((rc = grow_mesh_buffer(&m.sused, m.cap_sused, nv * 4))) return rc;
+    if ((rc = grow_mesh_buffer(&m.ssurvive, m.cap_ssurvive, nt * 4))) return rc;
+    if ((rc = grow_mesh_buffer(&m.vertex_map, m.cap_vertex_map, nv * 4))) return rc;
+    A.vertices = (const float*)m.vertices;
+    A.edges = (const uint32_t*)m.edges;
+    A.triangles = (const uint32_t*)m.triangles;
+    A.keys = (unsigned long long*)m.skeys;
+    // the key table filled with ones, used[] with zeros; keys, flags and the two prefix sums; the kept sizes reach the host; scatter into
+    // second buffers of exactly checked sizes; the flag reaches the host; then the second buffers ARE the mesh
+    HIP_TRY(hipMemsetAsync(m.skeys, 0xff, (size_t)simplify_key_bytes(A.n_clusters), st));
+    HIP_TRY(hipMemsetAsync(m.sused, 0, (size_t)nv * 4, st));
+    HIP_TRY(launch_simplify_mark(A, (uint32_t*)m.sused, (uint32_t*)m.ssurvive, (uint32_t*)m.codes, st));
+    HIP_TRY(launch_mesh_scan((const uint32_t*)m.codes, (uint32_t)n, (uint32_t*)m.vbase, (uint32_t*)m.tbase, m.partials, m.cc_words + 4, st));
+    HIP_TRY(hipMemsetAsync(m.cc_words + 3, 0, 4, st));
+    HIP_TRY(hipMemcpyAsync(kept, m.cc_words + 4, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (kept[0] > nv || kept[1] > nt) return fail(NRF_E_HIP, "nrf_simplify_mesh: the kept counts exceed the mesh");
+    if ((rc = grow_mesh_buffer(&m.vertices2, m.cap_vertices2, mesh_vertex_bytes(kept[0])))) return rc;
+    if ((rc = grow_mesh_buffer(&m.triangles2, m.cap_triangles2, mesh_triangle_bytes(kept[1])))) return rc;
+    if ((rc = grow_mesh_buffer(&m.edges2, m.cap_edges2, refine_edge_bytes(kept[0])))) return rc;
+    if ((rc = grow_mesh_buffer(&m.sources, m.cap_sources, (uint64_t)kept[0] * 4))) return rc;
+    uint32_t dropped = 0;
+    HIP_TRY(launch_simplify_scatter(A, (const uint32_t*)m.codes, (const uint32_t*)m.vbase, (const uint32_t*)m.tbase, kept[0], kept[1],
+                                    (float*)m.vertices2, (uint32_t*)m.edges2, (uint32_t*)m.sources, (uint32_t*)m.vertex_map,
+                                    (uint32_t*)m.triangles2, m.cc_words + 3, st));
+    HIP_TRY(hipMemcpyAsync(&dropped, m.cc_words + 3, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (dropped)
+      return fail(NRF_E_HIP, "nrf_simplify_mesh: the scan and the scatter pass disagree (the mesh changed during the call); writes were dropped");
+    std::swap(m.vertices, m.vertices2);
+    std::swap(m.cap_vertices, m.cap_vertices2);
+    std::swap(m.triangles, m.triangles2);
+    std::swap(m.cap_triangles, m.cap_triangles2);
+    std::swap(m.edges, m.edges2);
+    std::swap(m.cap_edges, m.cap_edges2);
+    m.n_vertices = kept[0];
+    m.n_triangles = kept[1];
+  }
+  m.n_vertices_before = nv;
+  m.have_simplify = true;
+  m.have_parts = false;
+  m.have_attr = false;
+  m.have_brackets = false;
+  out->n_vertices = m.n_vertices;
+  out->n_triangles = m.n_triangles;
+  out->n_vertices_before = nv;
+  out->n_triangles_before = nt;
+  out->vertices = m.n_vertices ? m.vertices : nullptr;
+  out->triangles = m.n_triangles ? m.triangles : nullptr;
+  out->edges = m.n_vertices ? m.edges : nullptr;
+  out->sources = m.n_vertices ? m.sources : nullptr;
+  out->vertex_map = nv ? m.vertex_map : nullptr;
+  out->factor = factor;
+  out->reserved = 0;
+  return NRF_OK;
+}
+
+int nrf_read_mesh_simplification(nrf_context* c, uint32_t* sources, uint32_t* vertex_map) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!c->mesh.have || !c->mesh.have_simplify)
+    return fail(NRF_E_STATE, "no simplification of the current mesh (call nrf_simplify_mesh after nrf_extract_mesh or nrf_filter_mesh)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const auto& m = c->mesh;
+  if (sources && m.n_vertices) HIP_TRY(hipMemcpy(sources, m.sources, (size_t)m.n_vertices * 4, hipMemcpyDeviceToHost));
+  if (vertex_map && m.n_vertices_before) HIP_TRY(hipMemcpy(vertex_map, m.vertex_map, (size_t)m.n_vertices_before * 4, hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

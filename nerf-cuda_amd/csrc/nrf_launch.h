@@ -164,6 +164,27 @@ hipError_t launch_meshcc_keep(const MeshccArgs& A, uint64_t min_triangles, uint3
 hipError_t launch_meshcc_scatter(const MeshccArgs& A, const float* vertices, const uint32_t* codes, const uint32_t* vnew, const uint32_t* tnew,
                                  uint32_t kept_vertices, uint32_t kept_triangles, float* vertices_out, uint32_t* triangles_out, uint32_t* flag,
                                  hipStream_t st, const uint32_t* edges = nullptr, uint32_t* edges_out = nullptr);
+// Simplification of an indexed mesh by vertex clustering on the extraction's lattice (nrf_kernels_simplify.hip, definition:
+// nrf_simplify_plan.h); n_vertices > 0.  Every launch is a streaming pass that needs nothing another workgroup writes during it.
+//   launch_simplify_mark     the key pass (one 64-bit atomic minimum per vertex into keys, which the caller has filled with ones), the
+//                            triangle pass (survive[t], and used[rep] = 1 for a survivor; used zeroed by the caller) and
+//                            codes[i], i < max(n_vertices, n_triangles): used[i] and survive[i] as a scan code word
+//   launch_simplify_scatter  kept vertices, their edge words and sources, vertex_map [n_vertices] and the remapped surviving triangles
+//                            into second buffers of kept_vertices / kept_triangles elements; *flag is set to 1 when a write was dropped
+//                            because it would have fallen outside those counts
+struct SimplifyArgs {
+  MeshLattice L;                         // the lattice of the extraction
+  uint32_t factor = 0, n_clusters = 0;   // n_clusters = simplify_clusters(L, factor)
+  uint32_t n_vertices = 0, n_triangles = 0;
+  const float* vertices = nullptr;       // [n_vertices][3]
+  const uint32_t* edges = nullptr;       // [n_vertices]
+  const uint32_t* triangles = nullptr;   // [n_triangles][3]
+  unsigned long long* keys = nullptr;    // [n_clusters]
+};
+hipError_t launch_simplify_mark(const SimplifyArgs& A, uint32_t* used, uint32_t* survive, uint32_t* codes, hipStream_t st);
+hipError_t launch_simplify_scatter(const SimplifyArgs& A, const uint32_t* codes, const uint32_t* vnew, const uint32_t* tnew, uint32_t kept_vertices,
+                                   uint32_t kept_triangles, float* vertices_out, uint32_t* edges_out, uint32_t* sources, uint32_t* vertex_map,
+                                   uint32_t* triangles_out, uint32_t* flag, hipStream_t st);
 hipError_t launch_density_positions(uint32_t H, float k, void* xyz, void* dir, hipStream_t st);
 hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int n_iterations, void* grid, hipStream_t st);
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,

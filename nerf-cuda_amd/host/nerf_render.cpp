@@ -665,6 +665,22 @@ NerfRender::MeshRefinement NerfRender::refine_mesh(uint32_t n_steps) {
   return out;
 }
 
+NerfRender::SimplifiedMesh NerfRender::simplify_mesh(uint32_t factor) {
+  if (m_ctx.size() != 1) throw std::runtime_error{"simplify_mesh: single-device renderers only"};
+  nrf_mesh_simplify s{};
+  check(nrf_simplify_mesh(m_ctx[0], factor, nullptr, &s), "nrf_simplify_mesh");
+  SimplifiedMesh out;
+  out.vertices.resize(3 * (size_t)s.n_vertices);
+  out.triangles.resize(3 * (size_t)s.n_triangles);
+  out.sources.resize((size_t)s.n_vertices);
+  out.vertex_map.resize((size_t)s.n_vertices_before);
+  check(nrf_read_mesh(m_ctx[0], out.vertices.data(), out.triangles.data()), "nrf_read_mesh");
+  check(nrf_read_mesh_simplification(m_ctx[0], out.sources.data(), out.vertex_map.data()), "nrf_read_mesh_simplification");
+  out.vertices_dev = s.vertices;
+  m_mesh_vertices = (size_t)s.n_vertices;
+  return out;
+}
+
 bool NerfRender::save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
                           const std::vector<float>& normals) {
   std::FILE* f = std::fopen(path.c_str(), "w");

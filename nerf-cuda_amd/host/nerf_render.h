@@ -137,6 +137,16 @@ class NerfRender {
     const void* vertices_dev = nullptr;
   };
   MeshRefinement refine_mesh(uint32_t n_steps);
+  // nrf_simplify_mesh (nerfhip.h): vertex clustering on the extraction's lattice, on the device -- the vertices whose lattice points
+  // share a block of factor^3 points (factor 1 .. 256) merge into the one nearest the block's centre, collapsed triangles and vertices
+  // nothing names any more are dropped, and the result is the context's mesh (filter_mesh, refine_mesh and mesh_attributes then see it)
+  // -> the simplified mesh as extract_mesh returns one, with sources [n] (the old id of every vertex, ascending) and vertex_map
+  // [vertices before] (the new id of every old vertex's representative, or 0xffffffff).  After filter_mesh and refine_mesh and before
+  // mesh_attributes is the intended order.  Synchronous; single device.
+  struct SimplifiedMesh : Mesh {
+    std::vector<uint32_t> sources, vertex_map;
+  };
+  SimplifiedMesh simplify_mesh(uint32_t factor);
   // Wavefront OBJ: "v x y z" per vertex, "vn x y z" per vertex when normals ([n][3]) has one per vertex, faces 1-based ("f a//a b//b c//c"
   // with normals, "f a b c" without).  Returns false when the file cannot be written.
   static bool save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,

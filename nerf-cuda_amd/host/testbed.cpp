@@ -12,6 +12,8 @@
 //   the component with the most triangles
 //   [--mesh_refine N] -- after the filter and before the attributes every vertex is moved along its lattice edge onto the iso value of
 //   the density network, N (0 .. 16) bisections and a secant step on the device (NerfRender::refine_mesh)
+//   [--mesh_simplify K] -- after the filter and the refinement and before the attributes the mesh is simplified on the device by vertex
+//   clustering on blocks of K^3 lattice points, K = 1 .. 256 (NerfRender::simplify_mesh)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -36,14 +38,18 @@ int main(int argc, char** argv) {
   unsigned long long mesh_min_triangles = 0;
   bool mesh_largest = false;
   int mesh_refine = -1;  // (off)
+  int mesh_simplify = 0;  // (off)
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
-      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine") && i + 1 < argc) {
+      if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine" ||
+           a == "--mesh_simplify") &&
+          i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
         else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
         else if (a == "--mesh_refine") mesh_refine = std::atoi(argv[++i]);
+        else if (a == "--mesh_simplify") mesh_simplify = std::atoi(argv[++i]);
         else if (a == "--mesh_min_triangles") mesh_min_triangles = std::strtoull(argv[++i], nullptr, 10);
         else mesh_iso = (float)std::atof(argv[++i]);
       } else if (a == "--mesh_largest") {
@@ -153,6 +159,19 @@ int main(int argc, char** argv) {
                     (unsigned long long)refined.unbracketed, std::chrono::duration<double>(r1 - r0).count());
         mesh.vertices = std::move(refined.vertices);
         mesh.vertices_dev = refined.vertices_dev;
+      }
+      if (mesh_simplify != 0) {
+        // down to a triangle budget, on the device, after the refinement (the representatives are vertices of the mesh: they stay on the
+        // iso-surface) and before the attributes (fewer vertices for the seven network passes each of them costs)
+        const size_t nv0 = mesh.vertices.size() / 3, nt0 = mesh.triangles.size() / 3;
+        const auto s0 = std::chrono::steady_clock::now();
+        NerfRender::SimplifiedMesh simplified = render->simplify_mesh((uint32_t)mesh_simplify);
+        const auto s1 = std::chrono::steady_clock::now();
+        std::printf("mesh simplify: factor %d, vertices %zu -> %zu, triangles %zu -> %zu, %f s\n", mesh_simplify, nv0, simplified.vertices.size() / 3,
+                    nt0, simplified.triangles.size() / 3, std::chrono::duration<double>(s1 - s0).count());
+        mesh.vertices = std::move(simplified.vertices);
+        mesh.triangles = std::move(simplified.triangles);
+        mesh.vertices_dev = simplified.vertices_dev;
       }
       if (mesh_path.size() >= 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0) {
         // normals and colours in one launch at the device vertices (a vertex within the step of the box's faces gets zeros)

@@ -206,6 +206,23 @@ class MeshRefine(C.Structure):
     ]
 
 
+class MeshSimplify(C.Structure):
+    """nrf_mesh_simplify: device pointers owned by the context, valid until the next extract_mesh, filter_mesh, simplify_mesh or close."""
+    _fields_ = [
+        ("n_vertices", C.c_uint64),
+        ("n_triangles", C.c_uint64),
+        ("n_vertices_before", C.c_uint64),
+        ("n_triangles_before", C.c_uint64),
+        ("vertices", C.c_void_p),    # float [n_vertices][3]: the context's mesh
+        ("triangles", C.c_void_p),   # uint32 [n_triangles][3]
+        ("edges", C.c_void_p),       # uint32 [n_vertices]: the kept vertices' edge words
+        ("sources", C.c_void_p),     # uint32 [n_vertices]: the old id of every kept vertex, ascending
+        ("vertex_map", C.c_void_p),  # uint32 [n_vertices_before]: the new id of every old vertex's representative, or 0xffffffff
+        ("factor", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64),
@@ -336,6 +353,8 @@ _SIGS = {
     "nrf_filter_mesh": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(Mesh)]),
     "nrf_refine_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MeshRefine)]),
     "nrf_read_mesh_refinement": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "nrf_simplify_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MeshSimplify)]),
+    "nrf_read_mesh_simplification": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -986,6 +1005,28 @@ class NerfHip:
         _check(self.lib.nrf_read_mesh_refinement(self.h, e.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                  b.ctypes.data_as(C.POINTER(C.c_float)) if brackets else None))
         return e, b
+
+    def simplify_mesh(self, factor: int, stream=None) -> MeshSimplify:
+        """nrf_simplify_mesh: merges the vertices of the current mesh whose lattice points share a block of factor^3 points (factor
+        1 .. 256) into the one nearest the block's centre, drops the triangles that collapse and the vertices nothing names any more,
+        and makes the result the context's mesh: read_mesh, filter_mesh, refine_mesh and mesh_attributes see it.  Every vertex of the
+        result is an old vertex, bit for bit, with its edge word.  The labelling, the attributes and the brackets of the mesh it
+        replaced are invalid afterwards.  Returns after completion."""
+        out = MeshSimplify()
+        _check(self.lib.nrf_simplify_mesh(self.h, C.c_uint32(int(factor)), C.c_void_p(stream or 0), C.byref(out)))
+        self._mesh_counts = (int(out.n_vertices), int(out.n_triangles))
+        self._mesh_parts_counts = (0, 0)
+        self._mesh_simplify_counts = (int(out.n_vertices), int(out.n_vertices_before))
+        return out
+
+    def read_mesh_simplification(self):
+        """nrf_read_mesh_simplification: (sources uint32 [n_vertices] = the old id of every vertex of the simplified mesh, ascending,
+        vertex_map uint32 [n_vertices_before] = the new id of every old vertex's representative, or 0xffffffff) of the last
+        simplify_mesh of the current mesh"""
+        nv, before = getattr(self, "_mesh_simplify_counts", (0, 0))
+        src, vmap = np.empty(nv, np.uint32), np.empty(before, np.uint32)
+        _check(self.lib.nrf_read_mesh_simplification(self.h, src.ctypes.data_as(C.POINTER(C.c_uint32)), vmap.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return src, vmap
 
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
