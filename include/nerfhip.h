@@ -785,6 +785,65 @@ typedef struct nrf_mesh_simplify {
 } nrf_mesh_simplify;
 int nrf_simplify_mesh(nrf_context* ctx, uint32_t factor, void* stream, nrf_mesh_simplify* out);
 int nrf_read_mesh_simplification(nrf_context* ctx, uint32_t* sources, uint32_t* vertex_map);
+/* (ABI 7, addition) The mesh texture: the colours of the full network baked into a per-triangle texture atlas of the context's current
+ * mesh, so that the resolution of its appearance is chosen independently of its triangle budget (one colour per vertex is all
+ * nrf_mesh_attributes hands out, and nrf_simplify_mesh lowers the vertex count).  A lane of the kernel makes its texel's position and
+ * direction itself; nothing but the counters leaves the device.  All integer arithmetic is exact; every fp32 operation is ONE rounding
+ * (no contraction), the division and the square root the correctly rounded IEEE ones, so a host can replay it:
+ *   parameters res = r texels along a triangle's legs, 2 <= r <= 256; width = the atlas width in texels, r + 2 <= width <= 16384.
+ *   cells      triangles are paired: pair q = t >> 1 owns a cell of (r + 2) x (r + 1) texels.  cols = width / (r + 2) (integer
+ *              division), rows = ceil(n_pairs / cols), height = rows * (r + 1); pair q's cell origin is (x0, y0) = ((q % cols) * (r + 2),
+ *              (q / cols) * (r + 1)).  height <= 16384 and width * height <= 2^26; an empty mesh has height 0.
+ *   ownership  a cell texel (i', j'), 0 <= i' <= r + 1, 0 <= j' <= r, belongs to the even triangle 2q with (i, j) = (i', j') if
+ *              i' + j' <= r, and otherwise to the odd triangle 2q + 1 with (i, j) = (r + 1 - i', r - j').  Each half holds
+ *              (r + 1)(r + 2) / 2 texels and the two tile the cell exactly.  The corners of a triangle (a, b, c) sit at the texel centres
+ *              (i, j) = (0, 0), (r - 1, 0), (0, r - 1); the texels with i + j = r, and (r, 0) and (0, r), lie one step outside the
+ *              hypotenuse and are evaluated at the extrapolated position in the triangle's plane: a bilinear fetch anywhere inside the
+ *              triangle reads texels of the same triangle only.
+ *   position   of texel (i, j) of triangle (a, b, c) with the mesh's CURRENT vertex positions va, vb, vc: s = (float)i / (float)(r - 1),
+ *              t = (float)j / (float)(r - 1), e1_k = vb_k - va_k, e2_k = vc_k - va_k, x_k = (va_k + s * e1_k) + t * e2_k: the products are
+ *              rounded, then the sums, in this order.
+ *   direction  n_x = e1_y * e2_z - e1_z * e2_y and cyclically: two rounded products and one rounded difference -- the outward face
+ *              normal by the extraction's orientation rule.  d = the unit direction of (-n_x, -n_y, -n_z) as nrf_point_attributes forms
+ *              one from a gradient (above; the negations are exact): the head-on viewing direction.  A degenerate triangle (l2 not finite
+ *              or < 2^-60) has d = (0, 0, 0) and is still coloured.  The network is given 0.5f * d_k (rounded), then + 0.5f (rounded).
+ *   guard      a texel is evaluated if and only if its triangle exists (t < n_triangles), names only vertices < n_vertices, and every
+ *              x_k is finite with |x_k| <= bound (the one-tap guard of nrf_density).  A refused texel is zeros in every plane and nothing
+ *              of it is gathered.  An index is checked before it becomes an address.
+ *   texel      (r, g, b, sigma) = nrf_network at (x, d), bit for bit.  rgba8 = u8(r) | u8(g) << 8 | u8(b) << 16 | 255 << 24 with the
+ *              8-bit rule of nrf_read_u8 ((unsigned char)(255.0 * x), saturating, NaN -> 0).  An atlas texel that no triangle owns or
+ *              whose texel was refused -- the right margin, the cells after the last pair, the odd half of the last cell when
+ *              n_triangles is odd -- is zeros in both planes: rgba8's alpha is the coverage mask.
+ *   uvs        float [n_triangles][3][2].  A corner at atlas texel (px, py) has u = ((float)px + 0.5f) / (float)width and
+ *              v = ((float)py + 0.5f) / (float)height (v grows with the atlas row).  Even triangle, corners a, b, c: (x0, y0),
+ *              (x0 + r - 1, y0), (x0, y0 + r - 1); odd: (x0 + r + 1, y0 + r), (x0 + 2, y0 + r), (x0 + r + 1, y0 + 1).
+ * nrf_mesh_texture_size: the height of the atlas of n_triangles at (res, width); host only, no context.
+ * nrf_bake_mesh_texture: bakes the context's current mesh -- after nrf_filter_mesh, nrf_refine_mesh and nrf_simplify_mesh is the intended
+ *   place -- into three buffers owned by the context; they grow as needed and stay valid until the next nrf_extract_mesh,
+ *   nrf_filter_mesh, nrf_refine_mesh, nrf_simplify_mesh, nrf_bake_mesh_texture or nrf_destroy.  Each of the first four invalidates the
+ *   texture: nrf_read_mesh_texture returns NRF_E_STATE until the mesh is baked again.  The mesh itself, its labelling, its attributes and
+ *   its refinement records are untouched.  n_refused counts the texels of existing triangles that the guard zeroed.  The work is enqueued
+ *   on `stream` (NULL: the context's) and the call returns after it has completed: n_refused has to reach the host.  An empty mesh is
+ *   NRF_OK with height 0 and NULL pointers.
+ * nrf_read_mesh_texture: host copies of the last bake: float [height][width][4], uint32 [height][width], float [n_triangles][3][2];
+ *   each may be NULL.
+ * NRF_E_INVALID: a NULL out (nrf_mesh_texture_size: height); res or width out of range; an atlas beyond the height or texel limits --
+ * the message names the smallest width that would fit, or says that none does.  NRF_E_STATE: no model loaded (also for a mesh made from
+ * a caller's lattice on a context without a model: there is no network to ask); no mesh extracted yet; nrf_read_mesh_texture: no texture
+ * of the current mesh.  A refused call writes nothing.  The calls take no slot of the 16 calls in flight, leave nrf_get_stats untouched
+ * and write none of the context's frame buffers.
+ * (csrc/nrf_bake_plan.h is this text as code.) */
+typedef struct nrf_mesh_texture {
+  uint32_t width, height, res, cols;
+  uint64_t n_triangles;
+  uint64_t n_refused; /* owned texels the guard zeroed */
+  void* texels;       /* device float4 [height][width] = (r, g, b, sigma) */
+  void* rgba8;        /* device uint32 [height][width] */
+  void* uvs;          /* device float [n_triangles][3][2] */
+} nrf_mesh_texture;
+int nrf_mesh_texture_size(uint64_t n_triangles, uint32_t res, uint32_t width, uint32_t* height); /* host only */
+int nrf_bake_mesh_texture(nrf_context* ctx, uint32_t res, uint32_t width, void* stream, nrf_mesh_texture* out);
+int nrf_read_mesh_texture(nrf_context* ctx, float* texels_f32x4, uint32_t* rgba8, float* uvs); /* each may be NULL */
 /* set_rays_o/d + kernel_near_far_from_aabb for every pixel (row-major):
  * rays_o [n][3], rays_d [n][3], nears [n], fars [n]                          */
 int nrf_generate_rays(nrf_context* ctx, const float cam[4], const float pose[16],

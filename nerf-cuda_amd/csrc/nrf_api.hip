@@ -193,6 +193,12 @@ struct nrf_context {
     size_t cap_skeys = 0, cap_sused = 0, cap_ssurvive = 0, cap_sources = 0, cap_vertex_map = 0;
     uint64_t n_vertices_before = 0;
     bool have_simplify = false;
+    // nrf_bake_mesh_texture: the atlas planes and the UVs of the mesh above, the counter of refused texels (device) and the layout and
+    // count of the last bake (have_texture falls with every nrf_extract_mesh, nrf_filter_mesh, nrf_refine_mesh and nrf_simplify_mesh)
+    void *texels = nullptr, *rgba8 = nullptr, *uvs = nullptr, *bake_count = nullptr;
+    size_t cap_texels = 0, cap_rgba8 = 0, cap_uvs = 0, cap_bake_count = 0;
+    BakeLayout texture{};
+    bool have_texture = false;
   } mesh;
 };
 
@@ -256,7 +262,7 @@ void free_mesh(nrf_context* c) {
   auto& m = c->mesh;
   for (void* q : {m.sigma, m.codes, m.vbase, m.tbase, m.partials, m.vertices, m.triangles, m.normals, m.colors, (void*)m.totals,
                   m.labels, m.rows, m.components, m.vertices2, m.triangles2, (void*)m.cc_words, m.edges, m.edges2, m.brackets,
-                  m.skeys, m.sused, m.ssurvive, m.sources, m.vertex_map})
+                  m.skeys, m.sused, m.ssurvive, m.sources, m.vertex_map, m.texels, m.rgba8, m.uvs, m.bake_count})
     if (q) (void)hipFree(q);
   m = nrf_context::MeshBuffers{};
 }
@@ -1871,6 +1877,7 @@ int nrf_extract_mesh(nrf_context* c, const nrf_lattice* lattice, float iso, cons
   auto& m = c->mesh;
   m.have = false;
   m.have_attr = false;
+  m.have_texture = false;
   m.have_parts = false;
   m.have_brackets = false;
   m.have_simplify = false;
@@ -2086,6 +2093,7 @@ int nrf_filter_mesh(nrf_context* c, uint64_t min_triangles, uint32_t flags, void
   }
   m.have_parts = false;
   m.have_attr = false;
+  m.have_texture = false;
   m.have_brackets = false;
   m.have_simplify = false;
   out->n_vertices = m.n_vertices;
@@ -2164,6 +2172,7 @@ int nrf_refine_mesh(nrf_context* c, uint32_t n_steps, void* stream, nrf_mesh_ref
   if (!m.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
   m.have_brackets = false;
   m.have_attr = false;
+  m.have_texture = false;
   const uint64_t nv = m.n_vertices;
   uint32_t open = 0;
   if (nv) {
@@ -2273,6 +2282,7 @@ int nrf_simplify_mesh(nrf_context* c, uint32_t factor, void* stream, nrf_mesh_si
   m.have_simplify = true;
   m.have_parts = false;
   m.have_attr = false;
+  m.have_texture = false;
   m.have_brackets = false;
   out->n_vertices = m.n_vertices;
   out->n_triangles = m.n_triangles;
@@ -2297,6 +2307,91 @@ int nrf_read_mesh_simplification(nrf_context* c, uint32_t* sources, uint32_t* ve
   const auto& m = c->mesh;
   if (sources && m.n_vertices) HIP_TRY(hipMemcpy(sources, m.sources, (size_t)m.n_vertices * 4, hipMemcpyDeviceToHost));
   if (vertex_map && m.n_vertices_before) HIP_TRY(hipMemcpy(vertex_map, m.vertex_map, (size_t)m.n_vertices_before * 4, hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// The mesh texture (nrf_kernels_bake.hip; the definition is nrf_bake_plan.h's).  Like the attributes: no slot of the 16-call ring, no
+// statistics, no frame buffer, and the mesh is only read; it returns after completion, because the count of refused texels has to
+// reach the host.
+static std::string bake_limit_message(const char* who, uint64_t n_triangles, uint32_t res, uint32_t width) {
+  const uint32_t fit = bake_smallest_width(n_triangles, res);
+  std::string msg = std::string(who) + ": the atlas of " + std::to_string(n_triangles) + " triangles at res " + std::to_string(res) + " and width " +
+                    std::to_string(width) + " would be " + std::to_string(bake_height64(n_triangles, res, width)) +
+                    " texels high (limits: height 16384, width * height 2^26); ";
+  msg += fit ? "the smallest width that fits is " + std::to_string(fit) : std::string("no width fits at this res");
+  return msg;
+}
+
+int nrf_mesh_texture_size(uint64_t n_triangles, uint32_t res, uint32_t width, uint32_t* height) {
+  if (!height) return fail(NRF_E_INVALID, "null argument");
+  if (!bake_params_valid(res, width)) return fail(NRF_E_INVALID, "nrf_mesh_texture_size: res must be 2 .. 256 and width res + 2 .. 16384");
+  BakeLayout B;
+  if (!bake_layout(n_triangles, res, width, B)) return fail(NRF_E_INVALID, bake_limit_message("nrf_mesh_texture_size", n_triangles, res, width));
+  *height = B.height;
+  return NRF_OK;
+}
+
+int nrf_bake_mesh_texture(nrf_context* c, uint32_t res, uint32_t width, void* stream, nrf_mesh_texture* out) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  if (!bake_params_valid(res, width)) return fail(NRF_E_INVALID, "nrf_bake_mesh_texture: res must be 2 .. 256 and width res + 2 .. 16384");
+  STAGE_PROLOGUE();  // (a mesh made from a caller's lattice on a context without a model has no network to ask: NRF_E_STATE)
+  auto& m = c->mesh;
+  if (!m.have) return fail(NRF_E_STATE, "no mesh extracted yet (call nrf_extract_mesh first)");
+  const uint64_t nt = m.n_triangles;
+  BakeLayout B;
+  if (!bake_layout(nt, res, width, B)) return fail(NRF_E_INVALID, bake_limit_message("nrf_bake_mesh_texture", nt, res, width));
+  m.have_texture = false;
+  uint32_t refused = 0;
+  if (nt) {
+    if ((rc = grow_mesh_buffer(&m.texels, m.cap_texels, bake_texel_bytes(B)))) return rc;
+    if ((rc = grow_mesh_buffer(&m.rgba8, m.cap_rgba8, bake_rgba8_bytes(B)))) return rc;
+    if ((rc = grow_mesh_buffer(&m.uvs, m.cap_uvs, bake_uv_bytes(nt)))) return rc;
+    if ((rc = grow_mesh_buffer(&m.bake_count, m.cap_bake_count, 4))) return rc;
+    BakeArgs A;
+    A.B = B;
+    A.n_vertices = (uint32_t)m.n_vertices;
+    A.bound = c->desc.bound;
+    A.vertices = (const float*)m.vertices;
+    A.triangles = (const uint32_t*)m.triangles;
+    A.texels = (float*)m.texels;
+    A.rgba8 = (uint32_t*)m.rgba8;
+    A.n_refused = (uint32_t*)m.bake_count;
+    // both planes and the counter cleared; the texels; the UVs; the count reaches the host
+    HIP_TRY(hipMemsetAsync(m.texels, 0, (size_t)bake_texel_bytes(B), st));
+    HIP_TRY(hipMemsetAsync(m.rgba8, 0, (size_t)bake_rgba8_bytes(B), st));
+    HIP_TRY(hipMemsetAsync(m.bake_count, 0, 4, st));
+    HIP_TRY(launch_bake(c->dm, A, st));
+    HIP_TRY(launch_bake_uvs(B, (float*)m.uvs, st));
+    HIP_TRY(hipMemcpyAsync(&refused, m.bake_count, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  m.texture = B;
+  m.have_texture = true;
+  out->width = B.width;
+  out->height = B.height;
+  out->res = B.res;
+  out->cols = B.cols;
+  out->n_triangles = nt;
+  out->n_refused = refused;
+  out->texels = nt ? m.texels : nullptr;
+  out->rgba8 = nt ? m.rgba8 : nullptr;
+  out->uvs = nt ? m.uvs : nullptr;
+  return NRF_OK;
+}
+
+int nrf_read_mesh_texture(nrf_context* c, float* texels, uint32_t* rgba8, float* uvs) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!c->mesh.have || !c->mesh.have_texture)
+    return fail(NRF_E_STATE, "no texture of the current mesh (call nrf_bake_mesh_texture after the last call that changed the mesh)");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const auto& m = c->mesh;
+  const BakeLayout& B = m.texture;
+  if (!B.n_triangles) return NRF_OK;
+  if (texels) HIP_TRY(hipMemcpy(texels, m.texels, (size_t)bake_texel_bytes(B), hipMemcpyDeviceToHost));
+  if (rgba8) HIP_TRY(hipMemcpy(rgba8, m.rgba8, (size_t)bake_rgba8_bytes(B), hipMemcpyDeviceToHost));
+  if (uvs) HIP_TRY(hipMemcpy(uvs, m.uvs, (size_t)bake_uv_bytes(B.n_triangles), hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

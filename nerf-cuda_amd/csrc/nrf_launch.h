@@ -4,6 +4,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "nrf_bake_plan.h"  // BakeLayout
 #include "nrf_grid_plan.h"  // persistent_lds_total: the sum plan_grid and launch_render share
 #include "nrf_mesh_plan.h"  // MeshLattice
 
@@ -185,6 +186,22 @@ hipError_t launch_simplify_mark(const SimplifyArgs& A, uint32_t* used, uint32_t*
 hipError_t launch_simplify_scatter(const SimplifyArgs& A, const uint32_t* codes, const uint32_t* vnew, const uint32_t* tnew, uint32_t kept_vertices,
                                    uint32_t kept_triangles, float* vertices_out, uint32_t* edges_out, uint32_t* sources, uint32_t* vertex_map,
                                    uint32_t* triangles_out, uint32_t* flag, hipStream_t st);
+// The mesh texture (nrf_kernels_bake.hip, definition: nrf_bake_plan.h): every texel of every pair's cell is one work item, a lane makes
+// its position and its direction itself from its triangle's three vertices, ONE full network pass per chunk of 64 texels.  Launch
+// sizes and LDS are launch_network's for the model's stage instance.  The caller has cleared texels and rgba8 on the same stream:
+// the kernel writes accepted texels only.  launch_bake_uvs: one thread per triangle.
+struct BakeArgs {
+  BakeLayout B;
+  uint32_t n_vertices = 0;
+  float bound = 0.f;
+  const float* vertices = nullptr;      // [n_vertices][3]
+  const uint32_t* triangles = nullptr;  // [B.n_triangles][3]
+  float* texels = nullptr;              // [B.height][B.width][4] = (r, g, b, sigma)
+  uint32_t* rgba8 = nullptr;            // [B.height][B.width]
+  uint32_t* n_refused = nullptr;        // += the owned texels the guard refused
+};
+hipError_t launch_bake(const DevModel& M, const BakeArgs& A, hipStream_t st);
+hipError_t launch_bake_uvs(const BakeLayout& B, float* uvs, hipStream_t st);
 hipError_t launch_density_positions(uint32_t H, float k, void* xyz, void* dir, hipStream_t st);
 hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int n_iterations, void* grid, hipStream_t st);
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,

@@ -5,6 +5,7 @@
 #include "nerf_render.h"
 
 #include "json_lite.h"
+#include "png_lite.h"
 #include "../csrc/nrf_attr_plan.h"  // (device-free: the 8-bit rule of an exported colour)
 
 #include <algorithm>
@@ -697,6 +698,59 @@ bool NerfRender::save_obj(const std::string& path, const std::vector<float>& ver
     else std::fprintf(f, "f %lu %lu %lu\n", a, b, c);
   }
   const bool ok = !std::ferror(f);
+  return std::fclose(f) == 0 && ok;
+}
+
+NerfRender::MeshTexture NerfRender::bake_mesh_texture(uint32_t res, uint32_t width) {
+  if (!m_have_network) throw std::runtime_error{"bake_mesh_texture: no network loaded"};
+  if (m_ctx.size() != 1) throw std::runtime_error{"bake_mesh_texture: single-device renderers only"};
+  nrf_mesh_texture t{};
+  check(nrf_bake_mesh_texture(m_ctx[0], res, width, nullptr, &t), "nrf_bake_mesh_texture");
+  MeshTexture out;
+  out.width = t.width;
+  out.height = t.height;
+  out.res = t.res;
+  out.refused = t.n_refused;
+  const size_t px = (size_t)t.width * t.height;
+  out.texels.resize(4 * px);
+  out.rgba8.resize(px);
+  out.uvs.resize(6 * (size_t)t.n_triangles);
+  check(nrf_read_mesh_texture(m_ctx[0], out.texels.data(), out.rgba8.data(), out.uvs.data()), "nrf_read_mesh_texture");
+  return out;
+}
+
+bool NerfRender::save_obj_textured(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
+                                   const std::vector<float>& uvs, const std::vector<uint32_t>& rgba8, uint32_t width, uint32_t height) {
+  const size_t nv = vertices.size() / 3, nt = triangles.size() / 3;
+  if (uvs.size() != 6 * nt || rgba8.size() != (size_t)width * height) return false;
+  // the three files share the path's stem; the OBJ and the MTL name their neighbour without its directory
+  const size_t slash = path.find_last_of("/\\"), dot = path.find_last_of('.');
+  const std::string stem = dot != std::string::npos && (slash == std::string::npos || dot > slash) ? path.substr(0, dot) : path;
+  const std::string base = slash == std::string::npos ? stem : stem.substr(slash + 1);
+  if (width && height) {
+    std::vector<uint8_t> rgb(3 * rgba8.size());
+    for (size_t i = 0; i < rgba8.size(); ++i)
+      for (int k = 0; k < 3; ++k) rgb[3 * i + k] = (uint8_t)(rgba8[i] >> (8 * k));
+    if (!pnglite::write((stem + ".png").c_str(), (int)width, (int)height, 3, rgb.data())) return false;
+  }
+  std::FILE* f = std::fopen((stem + ".mtl").c_str(), "w");
+  if (!f) return false;
+  std::fprintf(f, "newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 0\n");
+  if (width && height) std::fprintf(f, "map_Kd %s.png\n", base.c_str());
+  bool ok = !std::ferror(f);
+  if (std::fclose(f) != 0 || !ok) return false;
+  f = std::fopen(path.c_str(), "w");
+  if (!f) return false;
+  std::fprintf(f, "# %zu vertices, %zu triangles, atlas %u x %u\nmtllib %s.mtl\nusemtl baked\n", nv, nt, width, height, base.c_str());
+  for (size_t i = 0; i < nv; ++i) std::fprintf(f, "v %.9g %.9g %.9g\n", vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);
+  // (an image's first row is its top one, an OBJ's v = 0 its bottom one: v is flipped; 1 - v is rounded once)
+  for (size_t i = 0; i < 3 * nt; ++i) std::fprintf(f, "vt %.9g %.9g\n", uvs[2 * i], 1.0f - uvs[2 * i + 1]);
+  for (size_t i = 0; i < nt; ++i) {
+    const unsigned long a = triangles[3 * i] + 1ul, b = triangles[3 * i + 1] + 1ul, c = triangles[3 * i + 2] + 1ul;
+    const unsigned long t = 3ul * (unsigned long)i;
+    std::fprintf(f, "f %lu/%lu %lu/%lu %lu/%lu\n", a, t + 1, b, t + 2, c, t + 3);
+  }
+  ok = !std::ferror(f);
   return std::fclose(f) == 0 && ok;
 }
 

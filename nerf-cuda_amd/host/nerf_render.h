@@ -151,6 +151,24 @@ class NerfRender {
   // with normals, "f a b c" without).  Returns false when the file cannot be written.
   static bool save_obj(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
                        const std::vector<float>& normals = {});
+  // nrf_bake_mesh_texture (nerfhip.h): the colours of the full network on a per-triangle texture atlas of the current mesh, on the
+  // device -- res texels along a triangle's legs (2 .. 256), two triangles per cell of (res + 2) x (res + 1) texels, width / (res + 2)
+  // cells per atlas row -> host copies: texels [height][width][4] = (r, g, b, sigma), rgba8 [height][width] (alpha 255 where a
+  // triangle's texel was evaluated, 0 elsewhere), uvs [n_triangles][3][2] (v grows with the atlas row) and the count of texels the
+  // guard zeroed.  The mesh is only read; after filter_mesh, refine_mesh and simplify_mesh is the intended place.  Synchronous; single
+  // device.
+  struct MeshTexture {
+    uint32_t width = 0, height = 0, res = 0;
+    uint64_t refused = 0;
+    std::vector<float> texels, uvs;
+    std::vector<uint32_t> rgba8;
+  };
+  MeshTexture bake_mesh_texture(uint32_t res, uint32_t width);
+  // Wavefront OBJ with a texture: `path` ("v", three "vt u (1 - v)" per triangle, "f a/3t+1 b/3t+2 c/3t+3", 1-based), next to it
+  // <stem>.mtl (one material whose map_Kd names the image) and <stem>.png (the atlas's rgb, 8 bits, first row on top).  uvs is
+  // [n_triangles][3][2], rgba8 [height][width].  Returns false when the sizes disagree or a file cannot be written.
+  static bool save_obj_textured(const std::string& path, const std::vector<float>& vertices, const std::vector<uint32_t>& triangles,
+                                const std::vector<float>& uvs, const std::vector<uint32_t>& rgba8, uint32_t width, uint32_t height);
   // nrf_mesh_attributes (nerfhip.h): unit normals and colours at the vertices of the last extract_mesh, in one launch on the device
   // -> host normals [n][3] (outward, -g / |g|; zeros where the gradient is degenerate), colours [n][3] (the network's rgb, looked at
   // along -normal), sigmas [n] and |g| [n].  h is the step of the central differences; a vertex within h of the box's faces gets

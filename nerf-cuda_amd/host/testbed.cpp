@@ -14,6 +14,10 @@
 //   the density network, N (0 .. 16) bisections and a secant step on the device (NerfRender::refine_mesh)
 //   [--mesh_simplify K] -- after the filter and the refinement and before the attributes the mesh is simplified on the device by vertex
 //   clustering on blocks of K^3 lattice points, K = 1 .. 256 (NerfRender::simplify_mesh)
+//   [--mesh_texture R [--mesh_texture_width W]] -- with FILE.obj: after the filter, the refinement and the simplification, and in place
+//   of the attributes, the colours of the network are baked on the device into a per-triangle texture atlas of R (2 .. 256) texels along
+//   a triangle's legs and W (default 4096) texels width (NerfRender::bake_mesh_texture), and the mesh is written as FILE.obj with
+//   FILE.mtl and FILE.png next to it (save_obj_textured)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -39,17 +43,20 @@ int main(int argc, char** argv) {
   bool mesh_largest = false;
   int mesh_refine = -1;  // (off)
   int mesh_simplify = 0;  // (off)
+  int mesh_texture = 0, mesh_texture_width = 4096;  // (off)
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
       if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine" ||
-           a == "--mesh_simplify") &&
+           a == "--mesh_simplify" || a == "--mesh_texture" || a == "--mesh_texture_width") &&
           i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
         else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
         else if (a == "--mesh_refine") mesh_refine = std::atoi(argv[++i]);
         else if (a == "--mesh_simplify") mesh_simplify = std::atoi(argv[++i]);
+        else if (a == "--mesh_texture") mesh_texture = std::atoi(argv[++i]);
+        else if (a == "--mesh_texture_width") mesh_texture_width = std::atoi(argv[++i]);
         else if (a == "--mesh_min_triangles") mesh_min_triangles = std::strtoull(argv[++i], nullptr, 10);
         else mesh_iso = (float)std::atof(argv[++i]);
       } else if (a == "--mesh_largest") {
@@ -173,7 +180,17 @@ int main(int argc, char** argv) {
         mesh.triangles = std::move(simplified.triangles);
         mesh.vertices_dev = simplified.vertices_dev;
       }
-      if (mesh_path.size() >= 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0) {
+      const bool ply = mesh_path.size() >= 4 && mesh_path.compare(mesh_path.size() - 4, 4, ".ply") == 0;
+      if (mesh_texture != 0 && !ply) {
+        // the appearance at a resolution of its own, on the device: one network pass per texel, looked at head-on
+        const auto t0 = std::chrono::steady_clock::now();
+        const NerfRender::MeshTexture tex = render->bake_mesh_texture((uint32_t)mesh_texture, (uint32_t)mesh_texture_width);
+        const auto t1 = std::chrono::steady_clock::now();
+        std::printf("mesh texture: res %u, atlas %u x %u, %zu triangles, %llu texels refused, %f s\n", tex.res, tex.width, tex.height,
+                    tex.uvs.size() / 6, (unsigned long long)tex.refused, std::chrono::duration<double>(t1 - t0).count());
+        if (!NerfRender::save_obj_textured(mesh_path, mesh.vertices, mesh.triangles, tex.uvs, tex.rgba8, tex.width, tex.height))
+          throw std::runtime_error{"cannot write " + mesh_path};
+      } else if (ply) {
         // normals and colours in one launch at the device vertices (a vertex within the step of the box's faces gets zeros)
         const auto a0 = std::chrono::steady_clock::now();
         const NerfRender::MeshAttributes attr = render->mesh_attributes(b / 128.0f);

@@ -223,6 +223,22 @@ class MeshSimplify(C.Structure):
     ]
 
 
+class MeshTexture(C.Structure):
+    """nrf_mesh_texture: device pointers owned by the context, valid until the next extract_mesh, filter_mesh, refine_mesh,
+    simplify_mesh, bake_mesh_texture or close."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("res", C.c_uint32),
+        ("cols", C.c_uint32),
+        ("n_triangles", C.c_uint64),
+        ("n_refused", C.c_uint64),   # owned texels the guard zeroed
+        ("texels", C.c_void_p),      # float4 [height][width] = (r, g, b, sigma)
+        ("rgba8", C.c_void_p),       # uint32 [height][width]
+        ("uvs", C.c_void_p),         # float [n_triangles][3][2]
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("n_rays", C.c_uint64),
@@ -355,6 +371,9 @@ _SIGS = {
     "nrf_read_mesh_refinement": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "nrf_simplify_mesh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(MeshSimplify)]),
     "nrf_read_mesh_simplification": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nrf_mesh_texture_size": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "nrf_bake_mesh_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshTexture)]),
+    "nrf_read_mesh_texture": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "nrf_generate_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_march": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
@@ -662,6 +681,13 @@ def tiles_per_shard(width: int, height: int, shard_count: int) -> int:
     n = C.c_int()
     _check(load_library().nrf_tiles_per_shard(width, height, shard_count, C.byref(n)))
     return int(n.value)
+
+
+def mesh_texture_size(n_triangles: int, res: int, width: int) -> int:
+    """nrf_mesh_texture_size: the height of the atlas bake_mesh_texture makes of n_triangles at (res, width); host only"""
+    h = C.c_uint32()
+    _check(load_library().nrf_mesh_texture_size(C.c_uint64(int(n_triangles)), C.c_uint32(int(res)), C.c_uint32(int(width)), C.byref(h)))
+    return int(h.value)
 
 
 def _fptr(a):
@@ -1027,6 +1053,26 @@ class NerfHip:
         src, vmap = np.empty(nv, np.uint32), np.empty(before, np.uint32)
         _check(self.lib.nrf_read_mesh_simplification(self.h, src.ctypes.data_as(C.POINTER(C.c_uint32)), vmap.ctypes.data_as(C.POINTER(C.c_uint32))))
         return src, vmap
+
+    def bake_mesh_texture(self, res: int, width: int, stream=None) -> MeshTexture:
+        """nrf_bake_mesh_texture: the colours of the full network on a per-triangle texture atlas of the current mesh -- res texels
+        along a triangle's legs (2 .. 256), two triangles per cell of (res + 2) x (res + 1) texels, width / (res + 2) cells per atlas
+        row -- into buffers of the context: texels float4 [height][width] = (r, g, b, sigma), rgba8 uint32 [height][width] (alpha 255
+        where a triangle's texel was evaluated, 0 elsewhere) and uvs float [n_triangles][3][2].  The mesh is only read.  Returns after
+        completion; out.n_refused counts the texels of existing triangles that the guard zeroed."""
+        out = MeshTexture()
+        _check(self.lib.nrf_bake_mesh_texture(self.h, C.c_uint32(int(res)), C.c_uint32(int(width)), C.c_void_p(stream or 0), C.byref(out)))
+        self._mesh_texture_shape = (int(out.height), int(out.width), int(out.n_triangles))
+        return out
+
+    def read_mesh_texture(self):
+        """nrf_read_mesh_texture: (texels float32 [H][W][4], rgba8 uint32 [H][W], uvs float32 [T][3][2]) of the last bake_mesh_texture
+        of the current mesh"""
+        h, w, nt = getattr(self, "_mesh_texture_shape", (0, 0, 0))
+        tex, rgba, uvs = np.empty((h, w, 4), np.float32), np.empty((h, w), np.uint32), np.empty((nt, 3, 2), np.float32)
+        _check(self.lib.nrf_read_mesh_texture(self.h, tex.ctypes.data_as(C.POINTER(C.c_float)), rgba.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                              uvs.ctypes.data_as(C.POINTER(C.c_float))))
+        return tex, rgba, uvs
 
     def generate_rays(self, cam, pose, rays_o, rays_d, nears, fars, stream=None):
         cam = np.ascontiguousarray(cam, dtype=np.float32).reshape(4)
