@@ -242,7 +242,18 @@ inline int march_form(uint32_t H, uint32_t cascade, float bound) {
 #ifndef NRF_LDS_FRAG_DEPTH_GENERIC
 #define NRF_LDS_FRAG_DEPTH_GENERIC (NRF_LDS_FRAG_DEPTH > 1 ? 1 : NRF_LDS_FRAG_DEPTH)  // MARCH_GENERIC has no registers for two
 #endif
+// Pair gather of the static-plan instances (round 13; NRF_PAIR_GATHER=0 is the tile-major pass everywhere, for A/B builds): a
+// pass of two full tiles gathers both tiles step by step (nrf_render.h: pair_features) -- positions and level blocks read once
+// per pass, pair_window (tile, step) units in flight -- instead of tile 0's four steps, then tile 1's.  Four units are two
+// steps of both tiles (128 VGPRs under GATHER_QQFH, no scratch); MARCH_GENERIC has the registers for three (four: 12 bytes of
+// scratch under GATHER_QQFH).
+#ifndef NRF_PAIR_GATHER
+#define NRF_PAIR_GATHER 1
+#endif
 __host__ __device__ constexpr bool plan_levels(uint32_t gp) { return gp != GATHER_RUNTIME && NRF_LDS_PARAMS != 0; }
+__host__ __device__ constexpr int pair_window(uint32_t gp, int march) {  // 0: tile-major
+  return !plan_levels(gp) || NRF_PAIR_GATHER == 0 ? 0 : (march == MARCH_FORM_GENERIC ? 3 : 4);
+}
 __host__ __device__ constexpr int plan_frag_depth(uint32_t gp, int march) {
   return gp == GATHER_RUNTIME ? 0 : (march == MARCH_FORM_GENERIC ? NRF_LDS_FRAG_DEPTH_GENERIC : NRF_LDS_FRAG_DEPTH);
 }

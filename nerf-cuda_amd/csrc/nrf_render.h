@@ -304,8 +304,76 @@ __device__ __forceinline__ void sample_pos01(const DevModel& M, const float4 p, 
   }
 }
 
+// The features and direction values of a pass of TWO FULL tiles under a static gather plan, step-major (round 13, nrf_launch.h
+// pair_window).  Unit u = step u >> 1 of tile u & 1, eight to a pass, WIN of them in flight: the loads of units 0 .. WIN - 1 go
+// out, then unit u is interpolated as it lands and unit u + WIN takes its registers.  The pass has ONE exposed gather round trip
+// where the tile-major pass has one per tile, reads both positions and the level blocks of steps 0 and 1 in one LDS group and each
+// level block once (steps 2 and 3: one interpolation ahead of their first loads, so nothing waits for them).  Loads are issued
+// in the order the interpolation consumes them (the memory counter counts in issue order); the arithmetic of a feature is
+// network_from_lds's, call for call.  Both tiles are full -- the caller's wave-uniform branch --, so nothing is masked and the
+// pass is straight-line code.  Every unit is a scheduling region of its own: in one region, or with barriers that only hold
+// vector-memory instructions, the compiler sinks the interpolations' fp16 sums to the end of the pass and spills the ray state
+// (70 registers); the empty asm pins a unit's result ahead of the next unit's loads for the same reason.
+template <bool FAST, uint32_t GP, int PF, int WIN>
+__device__ __forceinline__ void pair_features(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W, int base, int lane,
+                                              half8_t (&feat)[2], half4_t (&dirf)[2], half8_t (&wpre)[PF > 0 ? PF : 1]) {
+  static_assert(WIN == 3 || WIN == 4, "units in flight");
+  const int g = lane >> 4, c = lane & 15;
+  const float4 p0 = W->pos[base + c], p1 = W->pos[base + 16 + c];
+  LevelParams PL[4];
+  PL[0] = plan_level<GP, 0>(lvs, g);
+  PL[1] = plan_level<GP, 1>(lvs, g);
+  __builtin_amdgcn_sched_barrier(0);
+  float px[2], py[2], pz[2];
+  sample_pos01(M, p0, px[0], py[0], pz[0]);
+  sample_pos01(M, p1, px[1], py[1], pz[1]);
+  uint32_t gv[WIN][8];
+  float gf[WIN][3];
+  uint32_t fb[2][4];
+#define NRF_PAIR_ISSUE(U)                                                                                                           \
+  gather_step_level<GP, ((U) >> 1)>(M, PL[(U) >> 1], px[(U) & 1], py[(U) & 1], pz[(U) & 1], gv[(U) % WIN], gf[(U) % WIN]);         \
+  __builtin_amdgcn_sched_barrier(0)
+#define NRF_PAIR_INTERP(U)                                                      \
+  fb[(U) & 1][(U) >> 1] = level_interp<FAST>(gv[(U) % WIN], gf[(U) % WIN]);     \
+  asm volatile("" : "+v"(fb[(U) & 1][(U) >> 1]))
+  // unit U lands; the level block of the step whose first unit goes out next is read ahead of the interpolation
+#define NRF_PAIR_ROLL(U)                                                                                                            \
+  if constexpr ((U) + WIN < 8 && (U) + WIN >= 4 && (((U) + WIN) & 1) == 0) PL[(((U) + WIN) >> 1) & 3] = plan_level<GP, (((U) + WIN) >> 1) & 3>(lvs, g); \
+  NRF_PAIR_INTERP(U);                                                                                                               \
+  __builtin_amdgcn_sched_barrier(0);                                                                                                \
+  if constexpr ((U) + WIN < 8) { NRF_PAIR_ISSUE(((U) + WIN) & 7); }
+  NRF_PAIR_ISSUE(0);
+  NRF_PAIR_ISSUE(1);
+  NRF_PAIR_ISSUE(2);
+  if constexpr (WIN == 4) { NRF_PAIR_ISSUE(3); }
+  NRF_PAIR_ROLL(0)
+  NRF_PAIR_ROLL(1)
+  NRF_PAIR_ROLL(2)
+  NRF_PAIR_ROLL(3)
+  NRF_PAIR_ROLL(4)
+  NRF_PAIR_ROLL(5)
+  const uint2 db0 = *reinterpret_cast<const uint2*>(&W->dirf[__builtin_bit_cast(int, p0.w)][2 * g]);
+  const uint2 db1 = *reinterpret_cast<const uint2*>(&W->dirf[__builtin_bit_cast(int, p1.w)][2 * g]);
+  NRF_PAIR_INTERP(6);
+  if constexpr (PF > 0) {
+    // the MLPs' first fragments, read while tile 1's last step is still to be interpolated (network_from_lds)
+    const LdsFrags frag{wl, lane};
+#pragma unroll
+    for (int f = 0; f < PF; ++f) wpre[f] = frag(FRAG_D0 + f);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  NRF_PAIR_INTERP(7);
+#undef NRF_PAIR_ROLL
+#undef NRF_PAIR_ISSUE
+#undef NRF_PAIR_INTERP
+  feat[0] = __builtin_bit_cast(half8_t, make_uint4(fb[0][0], fb[0][1], fb[0][2], fb[0][3]));
+  feat[1] = __builtin_bit_cast(half8_t, make_uint4(fb[1][0], fb[1][1], fb[1][2], fb[1][3]));
+  dirf[0] = __builtin_bit_cast(half4_t, db0);
+  dirf[1] = __builtin_bit_cast(half4_t, db1);
+}
+
 template <int NT, int RK = 1, bool FAST = false, int WD = 64, bool SHROWS = false, int DEPTH = 0, int GF = 0, uint32_t GP = GATHER_RUNTIME,
-          int PF = 0, bool DENS = false>
+          int PF = 0, bool DENS = false, int PAIR = 0>
 __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const float* rayd, int S, int base, int lane, float density_scale,
                                                  const half_t* rows = nullptr) {
@@ -315,6 +383,15 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
   half4_t dirf[NT];
   half8_t dirx[NT][RK_WIDE - 1];
   half8_t wpre[PF > 0 ? PF : 1];  // PF > 0: the first PF weight fragments, read behind the last tile's gathers (mlp_tiles)
+  if constexpr (PAIR != 0 && NT == 2) {
+    static_assert(plan_levels(GP) && GF == 0 && RK == 1 && WD == 64 && DEPTH == 0 && !DENS, "pair gathers exist for the static-plan hot instances only");
+    // two full tiles (wave-uniform): step-major.  A partly filled second tile keeps the tile-major pass below: masked units are
+    // basic blocks of their own, and the counted waits behind their joins wait for more than their unit (6 % slower, round 13)
+    if (S - base >= 32) {
+      pair_features<FAST, GP, PF, PAIR>(M, wl, lvs, W, base, lane, feat, dirf, wpre);
+      goto encoded;
+    }
+  }
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
     const int slot = base + 16 * n + c;
@@ -412,6 +489,7 @@ __device__ __forceinline__ void network_from_lds(const DevModel& M, const uint4*
     feat[n] = __builtin_bit_cast(half8_t, fv);
     dirf[n] = __builtin_bit_cast(half4_t, db);
   }
+encoded: __attribute__((unused));
   MlpOut<NT> o;
   if constexpr (DEPTH == 2) mlp_tiles_depth<NT, LdsFragsPlain, true>(LdsFragsPlain{wl, lane}, feat, dirf, o, M.rgb_output_activation == NRF_ACT_SIGMOID, M.depth_xd,
                                                                      M.depth_xr, M.density_activation, M.rgb_activation);
@@ -493,7 +571,7 @@ __device__ __forceinline__ void gen_network_from_lds(const DevModel& M, const Ge
 }
 
 // DENS: the density network alone (the RAYS_DENSITY instances)
-template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME, int PF = 0, bool DENS = false>
+template <int NET, bool FAST = false, uint32_t GP = GATHER_RUNTIME, int PF = 0, bool DENS = false, int PAIR = 0>
 __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4* wl, const LevelParams* lvs, WaveLds* W,
                                                  const GenLds& Lw, int S, int lane, float density_scale) {
   constexpr int RK = (NET == NET_WIDE || NET == NET_WIDE_SH) ? RK_WIDE : 1;
@@ -510,7 +588,7 @@ __device__ __forceinline__ void network_dispatch(const DevModel& M, const uint4*
       constexpr int DP = NET == NET_DEPTH ? 1 : (NET == NET_ACT ? 2 : 0);  // (2: runtime hidden activations)
       constexpr int GF = net_grid_f(NET);
       if (ntile <= 1 || NTM == 1) network_from_lds<1, RK, FAST, WD, SHR, DP, GF, GP, PF, DENS>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
-      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP, PF, DENS>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
+      else network_from_lds<NTM, RK, FAST, WD, SHR, DP, GF, GP, PF, DENS, PAIR>(M, wl, lvs, W, Lw.rayd, S, base, lane, density_scale, Lw.dir);
     }
   }
 }
@@ -953,7 +1031,7 @@ __device__ __forceinline__ void tile_rounds(const DevModel& M, const FrameParams
 
     if (S > 0) {
       // ---- network on the S queued samples (sample-major MFMA tiles)
-      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH), rays_density_like(RAYS)>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
+      network_dispatch<NET, FAST, GP, plan_frag_depth(GP, MARCH), rays_density_like(RAYS), pair_window(GP, MARCH)>(M, wl, lvs, W, lm.gen, S, lane, P.density_scale);
       wave_sync();
     }
     NRF_STAMP(t2);
