@@ -388,6 +388,9 @@ FOG_OPTIONS = {
     "dt_gamma0": (dict(dt_gamma=0.0), W3), "dt_gamma1_32": (dict(dt_gamma=1.0 / 32.0), W2),
     "perturb5": (dict(perturb=5), W3),
 }
+# the "stageoption" legs: stage WIDE, and under stage GENERIC a width instance, a grid instance and the catch-all
+FOG_STAGE_OPTION_INSTANCES = ("wide_freq12", "w32", "grid4_g4_8", "generic_w32_h2")
+FOG_STAGE_OPTIONS = ("max_steps7", "max_steps9", "density_scale0.37", "density_scale2", "min_near0.05", "dt_gamma0")
 FOG_LARGE = (333, 211)  # several strips per queue, and a tail that is split: a 64 x 48 frame is all tail
 
 
@@ -463,6 +466,18 @@ def _fog_legs():
                                          gather, W3, n_routes, opts_kw=dict(max_steps=max_steps) if max_steps else None,
                                          option="u8planes" if max_steps is None and cell != "generic_h" else None, table=T19,
                                          cell_kw=cell_kw), sched=plan_sched(cell), **plan_fields(plan, cell)))
+    # the options in the stages other than the hot one: the wide and the generic network pass apply density_scale in a line of their
+    # own, and every option leg above is the hot instance's.  Each instance renders the models of its own "instance" legs (same route
+    # set, same gather form); the scheduler alternates from option to option and from instance to instance, so that under the generic
+    # stage every option meets both kernel forms.
+    for i, iname in enumerate(FOG_STAGE_OPTION_INSTANCES):
+        plain = next(leg for leg in out if leg["family"] == "instance" and leg["instance"] == iname)
+        for k, oname in enumerate(FOG_STAGE_OPTIONS):
+            opts_kw, w = FOG_OPTIONS[oname]
+            leg = _fog_leg("stageoption", f"{iname}-{oname}", iname, ("persistent", "strip")[(i + k) % 2], plain["gather"], w,
+                           hot_n + list(INSTANCES).index(iname), opts_kw=opts_kw)
+            assert leg["routes"] == plain["routes"] and leg["stage"] != HOT
+            out.append(leg)
     return out
 
 

@@ -9,8 +9,9 @@ loop is put together here from its stage entry points:
     epilogue        get_image_and_depth (oracle/nerf_oracle.cpp `finish`)
 
 On the rays nrfo_generate_rays writes for a camera this is bit-identical to nrfo_render(.., SCHED_PER_RAY) of that camera
-(tests/test_render_rays_cpu.py) -- which pins this checker, not the feature.  density_scale must be 1: nrfo_network has no
-scale argument."""
+(tests/test_render_rays_cpu.py) -- which pins this checker, not the feature.  nrfo_network has no scale argument, so
+density_scale is applied here: sigma = float32(density_scale) * sigma, one fp32 product right after the network, skipped when the
+scale is 1 (network_one of oracle/nerf_oracle.cpp) -- bit for bit under every row of tests/render_options.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -50,11 +51,12 @@ def near_far(aabb, rays_o, rays_d, min_near):
     return near, far
 
 
-def render(oracle, desc, rays_o, rays_d, opts=None):
-    """rgba [n][4], depth [n], samples (the march-emitted samples = what the per-ray schedule composites) for n rays."""
+def render(oracle, desc, rays_o, rays_d, opts=None, apply_density_scale=True):
+    """rgba [n][4], depth [n], samples (the march-emitted samples = what the per-ray schedule composites) for n rays.
+    apply_density_scale=False leaves the multiply out: only for the test that shows the checker notices its absence."""
     opts = opts or nh.default_options()
-    assert opts.density_scale == 1.0, "nrfo_network has no density_scale argument"
     assert opts.perturb == 0
+    scale = np.float32(opts.density_scale)
     o = np.ascontiguousarray(rays_o, np.float32).reshape(-1, 3)
     d = np.ascontiguousarray(rays_d, np.float32).reshape(-1, 3)
     n = len(o)
@@ -72,6 +74,8 @@ def render(oracle, desc, rays_o, rays_d, opts=None):
         rgb = np.zeros((len(alive), 1, 3), np.float32)
         if found.any():
             s, c = oracle.network(xyz[found, 0], d[alive][found])
+            if apply_density_scale and opts.density_scale != 1.0:
+                s = (scale * np.asarray(s, np.float32)).astype(np.float32)
             sig[found, 0] = s
             rgb[found, 0] = c
         n_samples += int(found.sum())

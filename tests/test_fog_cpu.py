@@ -154,6 +154,16 @@ def test_fog_legs_cover_the_axes():
             opts[k].add(v)
     assert opts == dict(max_steps={1, 7, 8, 9, 37}, density_scale={0.37, 2.0}, bg_color={0.0, 0.25}, min_near={0.05},
                         dt_gamma={0.0, 1.0 / 32.0}, perturb={5})
+    # both stages other than the hot one under each of the six stage options, the generic one in both kernel forms and through a
+    # width instance, a grid instance and the catch-all
+    stage_legs = [leg for leg in pm.FOG_LEGS if leg["family"] == "stageoption"]
+    assert len(pm.FOG_STAGE_OPTIONS) == 6 and all(leg["instance"] != "hot" and leg["stage"] != pm.HOT for leg in stage_legs)
+    for oname in pm.FOG_STAGE_OPTIONS:
+        under = [leg for leg in stage_legs if leg["opts_kw"] == pm.FOG_OPTIONS[oname][0]]
+        assert all(leg["weight"] == pm.FOG_OPTIONS[oname][1] for leg in under), oname
+        assert {leg["stage"] for leg in under} == {pm.WIDE, pm.GENERIC}, oname
+        assert {leg["own"] for leg in under} >= {pm.WIDE, pm.W32, pm.GRID4, pm.GENERIC}, oname
+        assert {leg["sched"] for leg in under if leg["stage"] == pm.GENERIC} == {"persistent", "strip"}, oname
     assert {"fog-option-geometry-bound4_cascade3", "fog-option-geometry-ngp_aabb32", "fog-output-views3", "fog-output-shard1of3",
             "fog-output-u8", "fog-output-rays-persistent", "fog-output-rays-strip", "fog-large-persistent", "fog-large-strip"} <= set(ids)
     switches = [leg["env"] for leg in pm.FOG_LEGS if leg["family"] == "switch"]

@@ -11,7 +11,9 @@ the CPU that the oracle itself satisfies all of it for every leg, that no sigma 
 vacuously and that the bound sees a dropped sample, a stop threshold of 1e-3 and max_steps off by one.
 
 Measured worst error / bound (rgba and depth) per leg family on an MI355X, the oracle's own ratio on the same legs in brackets:
-    strength 0.56 (0.56), instance 0.41 (0.41), option 0.40 (0.40), switch 0.34 (0.34), output 0.34 (0.34), large 0.37 (0.37);
+    strength 0.56 (0.56), instance 0.41 (0.41), option 0.40 (0.40), switch 0.34 (0.34), output 0.34 (0.34), large 0.37 (0.37),
+    stageoption 0.40 (0.40): the options under the wide and generic stages; leg by leg the two ratios are equal but under
+    density_scale2 (0.19 .. 0.24 against the oracle's 0.18) and in generic_w32_h2 under max_steps 7 and 9 (0.18 against 0.16);
     chained nrf_composite: state 0.17, depth sum 0.22 (oracle 0.16 / 0.22).  `pytest -s` prints every frame's ratios.
 
 The "fog-plan-" legs (probe_model.PLANS x PLAN_CELLS) run the hot instance's three static gather plans in every march cell, with

@@ -145,33 +145,46 @@ RW, RH = 64, 48
 _checked = {}
 
 
-def _checker(model, kind):
-    """The checker's frame of the ramp scene, computed once per (model, limit) and shared: desc, rays, the limit, rgba, depth,
-    samples, raw depth, (near', far'), and the unlimited checker frame."""
+def _checker(model, kind, opts_kw=None):
+    """The checker's frame of the ramp scene, computed once per (model, limit, options) and shared: desc, rays, the limit, rgba,
+    depth, samples, raw depth, (near', far'), and the unlimited checker frame.  opts_kw: nrf_options fields other than the defaults
+    (the rays of a camera do not depend on them)."""
+    tag = tuple(sorted((opts_kw or {}).items()))
+    opts = nh.default_options()
+    for k, v in (opts_kw or {}).items():
+        setattr(opts, k, v)
     if ("desc", model) not in _checked:
         desc, keep, _ = models.build_model(log2_hashmap_size=12, H=32, **{**SMALL, **WIDE}[model])
         orc = op.Oracle(desc)
         o, d, _, _ = orc.generate_rays(syn.default_camera(RW, RH), syn.orbit_pose(30, 30), RW, RH)
-        _checked[("desc", model)] = (desc, keep, orc, o, d, ro.render(orc, desc, o, d))
-    desc, keep, orc, o, d, full = _checked[("desc", model)]
-    if (model, kind) not in _checked:
+        _checked[("desc", model)] = (desc, keep, orc, o, d)
+    desc, keep, orc, o, d = _checked[("desc", model)]
+    if ("full", model, tag) not in _checked:
+        _checked[("full", model, tag)] = ro.render(orc, desc, o, d, opts)
+    full = _checked[("full", model, tag)]
+    if (model, kind, tag) not in _checked:
         t = rco.ramp(RW, RH)
         lim = {kind: t}
-        res = rco.render(orc, desc, o, d, **lim)
-        nf = rco.near_far(desc, o, d, nh.default_options().min_near, **lim)
+        res = rco.render(orc, desc, o, d, opts, **lim)
+        nf = rco.near_far(desc, o, d, opts.min_near, **lim)
         for a in (*res[:2], res[3], *nf, t):
             a.setflags(write=False)
-        _checked[(model, kind)] = (t, res, nf)
-    return (desc, o, d, full) + _checked[(model, kind)]
+        _checked[(model, kind, tag)] = (t, res, nf)
+    return (desc, o, d, full) + _checked[(model, kind, tag)]
 
 
 @pytest.mark.parametrize("kind", ["t_max", "t_min"])
 @pytest.mark.parametrize("sched", list(SCHED))
 @pytest.mark.parametrize("model", list(SMALL))
 def test_the_ramp_matches_the_checker(model, sched, kind):
-    desc, o, d, full, t, (want, wdepth, n, raw), (near, far) = _checker(model, kind)
+    _ramp_matches_the_checker(model, sched, kind)
+
+
+def _ramp_matches_the_checker(model, sched, kind, opts_kw=None):
+    """opts_kw: nrf_options fields the context renders under and the checker is computed with (None: the defaults)"""
+    desc, o, d, full, t, (want, wdepth, n, raw), (near, far) = _checker(model, kind, opts_kw)
     W, H = RW, RH
-    ctx = _context(desc, W, H, SCHED[sched])
+    ctx = _context(desc, W, H, SCHED[sched], **(opts_kw or {}))
     assert _rays_instance(ctx) == (16 if sched == "persistent" else 0)
     do, dd = _upload(o), _upload(d)
     rgba, depth, st = _clipped(ctx, do, dd, W * H, **{kind: t})

@@ -114,9 +114,10 @@ def test_every_stage_has_a_ray_instance(name, kw, code):
     ctx.close()
 
 
-def _check_against_oracle(ctx, desc, o, d, W, H, min_cover, what):
+def _check_against_oracle(ctx, desc, o, d, W, H, min_cover, what, opts=None):
+    """opts: the options the context renders under (None: the defaults), handed to the assembled oracle"""
     orc = op.Oracle(desc)
-    want, wdepth, n = ro.render(orc, desc, o, d)
+    want, wdepth, n = ro.render(orc, desc, o, d, opts)
     want, wdepth = want.reshape(H, W, 4), wdepth.reshape(H, W)
     cover = float(np.mean(want[..., 3] > 0.5))
     print(f"{what}: oracle samples {n}, pixels with alpha > 0.5: {cover:.3f}")
