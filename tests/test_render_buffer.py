@@ -219,3 +219,159 @@ def test_present_is_bit_exact_against_the_oracle_where_no_power_function_is_invo
         np.testing.assert_array_equal(acc.reshape(-1, 4), acc_ref)
         np.testing.assert_array_equal(sur.reshape(-1, 4), op.rb_tonemap(acc_ref, 0.75, bg, nh.CS_LINEAR, nh.CS_LINEAR, curve))
     rb.close()
+
+
+# ---------------------------------------------------------------- planes beyond one trip of the kernels
+# rb_grid caps a launch at 2048 blocks of 256 threads (524 288 pixels), grid_for likewise: a 1031 x 1021 plane -- 1 052 651 pixels, odd
+# in both directions -- takes two full trips of present_kernel, overlay_depth_kernel and the quantize kernels and a ragged third
+BIG_W, BIG_H = 1031, 1021
+assert BIG_W * BIG_H > 2 * 524288 and BIG_W * BIG_H % 524288 != 0
+
+
+def _packed(sur):
+    rgb8, a8 = op.quantize_u8(sur.reshape(-1, 4), sur.reshape(-1, 4)[:, 3].copy())
+    return (rgb8[:, 0].astype(np.uint32) | (rgb8[:, 1].astype(np.uint32) << 8) | (rgb8[:, 2].astype(np.uint32) << 16) |
+            (a8.astype(np.uint32) << 24))
+
+
+def _big_frame(rng):
+    return (rng.random((BIG_H * BIG_W, 4), dtype=np.float32) * np.float32(1.6) - np.float32(0.1)).astype(np.float32)
+
+
+@pytest.mark.gpu
+def test_present_takes_every_trip_of_a_large_plane_bit_exact_against_the_oracle():
+    """Linear spaces and the ACES curve over two samples on the 1031 x 1021 plane: mean plane and surface bit for bit the oracle's
+    (as the small test above), the packed 8-bit plane the library's 8-bit rule applied to the surface."""
+    torch = pytest.importorskip("torch")
+    rb = nh.RenderBuffer(0)
+    rb.resize(BIG_W, BIG_H)
+    rb.set_color_space(nh.CS_LINEAR)
+    rb.set_tonemap_curve(nh.TM_ACES)
+    frame_p, _, _, _ = rb.buffers()
+    rgba8 = torch.zeros((BIG_H, BIG_W), dtype=torch.int32, device="cuda")
+    rng = np.random.default_rng(31)
+    acc_ref = np.zeros((BIG_H * BIG_W, 4), np.float32)
+    bg = [0.25, 0.5, 0.75, 0.6]
+    for spp in range(2):
+        frame = _big_frame(rng)
+        _upload(frame_p, frame)
+        rb.present(0.75, bg, nh.CS_LINEAR, rgba8.data_ptr())
+        acc_ref = op.rb_accumulate(frame, acc_ref, spp, nh.CS_LINEAR)
+        acc, sur = rb.read()
+        np.testing.assert_array_equal(acc.reshape(-1, 4).view(np.uint32), acc_ref.view(np.uint32))
+        want = op.rb_tonemap(acc_ref, 0.75, bg, nh.CS_LINEAR, nh.CS_LINEAR, nh.TM_ACES)
+        np.testing.assert_array_equal(sur.reshape(-1, 4).view(np.uint32), want.view(np.uint32))
+        np.testing.assert_array_equal(rgba8.cpu().numpy().view(np.uint32).reshape(-1), _packed(want))
+    assert rb.spp() == 2
+    rb.close()
+
+
+@pytest.mark.gpu
+def test_present_is_accumulate_plus_tonemap_on_a_large_plane():
+    """The sRGB row of the small test on the 1031 x 1021 plane: the fused pass and the two calls leave the same bits in every pixel."""
+    torch = pytest.importorskip("torch")
+    cs, ocs, curve, exposure = 0, 1, 1, 0.5
+    two, one = nh.RenderBuffer(0), nh.RenderBuffer(0)
+    for rb in (two, one):
+        rb.resize(BIG_W, BIG_H)
+        rb.set_color_space(cs)
+        rb.set_tonemap_curve(curve)
+    f2, _, _, _ = two.buffers()
+    f1, _, a1, _ = one.buffers()
+    _upload(a1, np.full((BIG_H * BIG_W, 4), np.nan, np.float32))
+    rgba8 = torch.zeros((BIG_H, BIG_W), dtype=torch.int32, device="cuda")
+    rng = np.random.default_rng(32)
+    bg = [0.3, 0.6, 0.9, 0.8]
+    for spp in range(2):
+        frame = _big_frame(rng)
+        _upload(f2, frame)
+        _upload(f1, frame)
+        two.accumulate(0.0)
+        two.tonemap(exposure, bg, ocs)
+        one.present(exposure, bg, ocs, rgba8.data_ptr())
+        acc2, sur2 = two.read()
+        acc1, sur1 = one.read()
+        assert not np.isnan(acc1).any() and np.abs(sur1).max() > 0
+        np.testing.assert_array_equal(acc1.view(np.uint32), acc2.view(np.uint32))
+        np.testing.assert_array_equal(sur1.view(np.uint32), sur2.view(np.uint32))
+        np.testing.assert_array_equal(rgba8.cpu().numpy().view(np.uint32).reshape(-1), _packed(sur1))
+    two.close()
+    one.close()
+
+
+@pytest.mark.gpu
+def test_overlay_depth_takes_every_trip_of_a_large_plane():
+    import torch
+    alpha, fov_axis, zoom, center = 0.35, 1, 1.7, (0.42, 0.61)
+    rb = nh.RenderBuffer(0)
+    iw, ih = 80, 60
+    rb.resize(BIG_W, BIG_H)
+    depth = np.random.default_rng(33).random((ih, iw), dtype=np.float32) * 1.3 - 0.1
+    d_d = torch.from_numpy(depth).cuda()
+    torch.cuda.synchronize()
+    rb.set_color_space(nh.CS_LINEAR)
+    rb.tonemap(0.0, (0.2, 0.4, 0.6, 1.0), nh.CS_LINEAR)
+    _, before = rb.read()
+    assert np.all(before == before[0, 0]) and before.max() > 0
+    rb.overlay_depth(alpha, d_d.data_ptr(), 0.9, iw, ih, fov_axis, zoom, center)
+    _, after = rb.read()
+    want = op.rb_overlay_depth(before, alpha, depth, 0.9, fov_axis, zoom, center)
+    np.testing.assert_allclose(after, want, rtol=0, atol=1e-6)
+    changed = np.any(after != before, axis=2).reshape(-1)
+    assert changed[:524288].any() and changed[524288:2 * 524288].any() and changed[2 * 524288:].any()  # the image reaches every trip
+    rb.close()
+
+
+@pytest.mark.gpu
+def test_quantize_entry_points_take_every_trip_of_a_large_plane():
+    torch = pytest.importorskip("torch")
+    n = BIG_W * BIG_H
+    rng = np.random.default_rng(34)
+    rgba = rng.uniform(-0.2, 1.3, (n, 4)).astype(np.float32)
+    depth = rng.uniform(-0.2, 1.3, n).astype(np.float32)
+    for at in (5, 524288 + 5, n - 9):
+        rgba[at, 0], rgba[at + 1, 1], rgba[at + 2, 2], depth[at + 3] = np.nan, np.inf, -np.inf, np.nan
+    rgb8_w, d8_w = op.quantize_u8(rgba, depth)
+    ctx = nh.NerfHip(0)
+    t_rgba, t_depth = torch.from_numpy(rgba).cuda(), torch.from_numpy(depth).cuda()
+    rgb8 = torch.zeros((n, 3), dtype=torch.uint8, device="cuda")
+    d8 = torch.zeros((n,), dtype=torch.uint8, device="cuda")
+    packed = torch.zeros((n,), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    ctx.quantize_u8(t_rgba.data_ptr(), t_depth.data_ptr(), n, rgb8.data_ptr(), d8.data_ptr())
+    ctx.quantize_rgbd8(t_rgba.data_ptr(), t_depth.data_ptr(), n, packed.data_ptr())
+    np.testing.assert_array_equal(rgb8.cpu().numpy(), rgb8_w)
+    np.testing.assert_array_equal(d8.cpu().numpy(), d8_w)
+    want = (rgb8_w[:, 0].astype(np.uint32) | (rgb8_w[:, 1].astype(np.uint32) << 8) | (rgb8_w[:, 2].astype(np.uint32) << 16) |
+            (d8_w.astype(np.uint32) << 24))
+    np.testing.assert_array_equal(packed.cpu().numpy().view(np.uint32), want)
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_host_image_to_accumulate_buffer():
+    """nrf_rb_host_to_accumulate_buffer (render_buffer.cu's host_to_accumulate_buffer): 8-bit rgb -> float(v) / 255.0 in double, rounded
+    to fp32, alpha 1; an identity development over a transparent background reproduces it on the surface."""
+    W, H = 67, 41
+    rb = nh.RenderBuffer(0)
+    rb.resize(W, H)
+    rng = np.random.default_rng(35)
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    img.reshape(-1)[:256] = np.arange(256, dtype=np.uint8)
+    assert len(np.unique(img)) == 256
+    rb.host_to_accumulate_buffer(img)
+    want = np.ones((H, W, 4), np.float32)
+    want[..., :3] = (img.astype(np.float64) / 255.0).astype(np.float32)
+    rb.set_color_space(nh.CS_LINEAR)
+    rb.set_tonemap_curve(nh.TM_IDENTITY)
+    rb.tonemap(0.0, [0, 0, 0, 0], nh.CS_LINEAR)
+    acc, sur = rb.read()
+    np.testing.assert_array_equal(acc.view(np.uint32), want.view(np.uint32))
+    np.testing.assert_array_equal(sur.view(np.uint32), want.view(np.uint32))
+    for bad in (img.reshape(-1)[:-3], np.concatenate([img.reshape(-1), np.zeros(3, np.uint8)])):  # a pixel short, a pixel long
+        with pytest.raises(nh.NerfHipError) as e:
+            rb.host_to_accumulate_buffer(bad)
+        assert e.value.code == nh.NRF_E_INVALID
+    acc2, _ = rb.read()
+    np.testing.assert_array_equal(acc2.view(np.uint32), want.view(np.uint32))  # a refused call wrote nothing
+    rb.close()
