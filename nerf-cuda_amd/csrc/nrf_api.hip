@@ -114,6 +114,16 @@ struct nrf_context {
   bool allow_gen_fast_grid = true;  // NRF_GEN_FAST_GRID=0: the generic instance always encodes with gen_level (A/B runs)
   int march_ff = 1;            // NRF_MARCH_FF=0: no barrier fast-forward ahead of t_skip (A/B runs, equality tests)
   int tail_split = 1;          // NRF_TAIL_SPLIT=0: no tail splitting in the persistent kernel (A/B runs)
+  // The barrier fast-forward's step tables (nrf_step_plan.h), one per (min_near, dt_gamma, bound, H) a call has rendered with: built
+  // and uploaded once into a buffer of its own, never rewritten (a launch in flight may still read it), freed with the context.
+  struct StepTable {
+    uint32_t key[4];
+    float* d = nullptr;
+    int n = 0;
+  };
+  std::vector<StepTable> step_tables;
+  bool allow_step_table = true;              // NRF_STEP_TABLE=0: every launch gets a null table and steps (A/B runs, equality tests)
+  int step_table_cap = STEP_TABLE_CAPACITY;  // NRF_STEP_TABLE_CAP=n: tables of n entries (tests: targets beyond the table at small shapes)
   void* d_rgb8 = nullptr;
   void* d_depth8 = nullptr;
   void* bound_rgba = nullptr;  // caller-owned targets (nrf_bind_output)
@@ -332,6 +342,42 @@ int fill_frame_params(nrf_context* c, const float cam[4], const float pose[16], 
   return NRF_OK;
 }
 
+// The step table of a call's options and the loaded model (nrf_step_plan.h): where launch_render hands it to the persistent
+// kernel.  Cached per context under the bits of its four inputs; a new key is built on the host and uploaded once.  tab stays
+// null when the switch is off or the inputs have no table: the kernel steps.
+constexpr size_t STEP_TABLES_MAX = 64;  // distinct option sets a context keeps tables for; beyond that all are dropped and rebuilt
+int step_table_for(nrf_context* c, const FrameParams& P, const float*& tab, int& n) {
+  tab = nullptr;
+  n = 0;
+#if NRF_STEP_TABLE
+  if (!c->allow_step_table) return NRF_OK;
+  const uint32_t key[4] = {step_bits(P.min_near), step_bits(P.dt_gamma), step_bits(c->dm.bound), c->dm.H};
+  for (const auto& s : c->step_tables)
+    if (std::memcmp(s.key, key, sizeof(key)) == 0) {
+      tab = s.d;
+      n = s.n;
+      return NRF_OK;
+    }
+  if (c->step_tables.size() >= STEP_TABLES_MAX) {
+    HIP_TRY(hipDeviceSynchronize());  // nothing may still be reading the tables that go
+    for (auto& s : c->step_tables) if (s.d) (void)hipFree(s.d);
+    c->step_tables.clear();
+  }
+  std::vector<float> members((size_t)STEP_TABLE_CAPACITY);
+  nrf_context::StepTable s;
+  std::memcpy(s.key, key, sizeof(key));
+  s.n = step_table(P.min_near, P.dt_gamma, c->dm.bound, c->dm.H, c->step_table_cap, members.data());
+  if (s.n > 0) {
+    HIP_TRY(hipMalloc((void**)&s.d, (size_t)s.n * 4));
+    HIP_TRY(hipMemcpy(s.d, members.data(), (size_t)s.n * 4, hipMemcpyHostToDevice));
+  }
+  c->step_tables.push_back(s);  // (n == 0: these inputs have no table, remembered as well)
+  tab = s.d;
+  n = s.n;
+#endif
+  return NRF_OK;
+}
+
 // The grid side of the plan (nrf_grid_plan.h), decided without a device like plan_model (nrf_debug_grid_plan:
 // tests/test_grid_plan_cpu.py): the march tables of a density grid, which of them are staged in LDS, and the workgroup that
 // renders the frames beside them -- own / stage / gen_wave_bytes: plan_model's; gen_frag_bytes: DevModel's.
@@ -499,6 +545,8 @@ int nrf_create(int device, nrf_context** out) {
   }
   if (const char* e = std::getenv("NRF_SAMPLE_CAP")) { c->sample_cap = std::atoi(e); c->sample_cap_forced = true; }
   if (const char* e = std::getenv("NRF_PERSISTENT")) c->allow_persistent = std::atoi(e) != 0;
+  if (const char* e = std::getenv("NRF_STEP_TABLE")) c->allow_step_table = std::atoi(e) != 0;
+  if (const char* e = std::getenv("NRF_STEP_TABLE_CAP")) c->step_table_cap = std::max(2, std::min(std::atoi(e), (int)STEP_TABLE_CAPACITY));
   if (const char* e = std::getenv("NRF_GATHER_PLAN")) c->allow_gather_plan = std::atoi(e) != 0;
   if (const char* e = std::getenv("NRF_CENTRE_OUT")) c->centre_out = std::atoi(e) != 0;
   if (const char* e = std::getenv("NRF_GEN_WLDS")) c->allow_gen_wlds = std::atoi(e) != 0;
@@ -551,6 +599,7 @@ int nrf_destroy(nrf_context* c) {
   free_frame(c);
   free_host_slots(c);
   free_mesh(c);
+  for (auto& s : c->step_tables) if (s.d) (void)hipFree(s.d);
   for (auto& h : c->hs) {
     if (h.done) (void)hipEventDestroy(h.done);
     for (hipEvent_t g : h.grp) if (g) (void)hipEventDestroy(g);
@@ -794,6 +843,12 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
   c->call_index = (c->call_index + 1) % CALL_RING;
   char* counters = call_slot(c, c->call_index);
   unsigned* plan = (c->plan_max_pos > 0 && prog == nullptr && rays == nullptr) ? (unsigned*)((char*)c->d_plan + (size_t)c->call_index * PLAN_BYTES) : nullptr;
+  const float* step_tab = nullptr;
+  int step_n = 0;
+  if (P.march_ff != 0) {  // (the fast-forward is the table's only reader)
+    const int rc = step_table_for(c, P, step_tab, step_n);
+    if (rc) return rc;
+  }
   HIP_TRY(hipEventRecord(c->ev0, st));  // (render_ms covers the clearing of the call's counters and the planning of its queues)
   const int per_launch = views_per_launch(P.tiles_x, P.tiles_y, MAX_VIEWS);  // NRF_MAX_VIEWS, fewer for frames beyond 8K
   const size_t px_bytes_a = out_mode == OUT_U8 ? 3 : 16, px_bytes_b = out_mode == OUT_U8 ? 1 : 4;
@@ -840,7 +895,7 @@ int render_views_impl(nrf_context* c, int n_views, const float* cams, const floa
     }
     HIP_TRY(launch_render(dm, P, VB, rgba ? (char*)rgba + (size_t)first * stride_px * px_bytes_a : nullptr,
                           (char*)depth + (size_t)first * stride_px * px_bytes_b, counters, st, first == 0, plan,
-                          (unsigned)c->plan_max_pos));
+                          (unsigned)c->plan_max_pos, step_tab, step_n));
   }
   c->last_views = n_views;
   HIP_TRY(hipEventRecord(c->ev1, st));
@@ -1334,6 +1389,48 @@ extern "C" int nrf_debug_march_form(uint32_t H, uint32_t cascade, float bound, u
   if (!out || H == 0 || cascade == 0 || !(bound > 0.0f)) return fail(NRF_E_INVALID, "bad argument");
   out[0] = (uint32_t)march_form(H, cascade, bound);
   out[1] = march_coarse_shift(H) ? 1u : 0u;
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): the step plan (nrf_step_plan.h) without a device -- step_table of the four inputs
+// into table[capacity] (capacity <= 1024; *n_out = its entries), then step_land of every (starts[i], targets[i]) on that table
+// into landed[i] -- of min(targets[i], far) when far is finite, as the fast-forward functions clamp their barrier to the ray's
+// far (an unclamped +inf target has no answer: the loop never ends once t + dt == t).  lds[0..2] (null: skipped) = a launch's LDS bytes without the table, the table's entries and a compute unit's
+// LDS: lds[3] = step_table_lds_offset of them.  tests/test_step_table_cpu.py.
+extern "C" int nrf_debug_step_table(float min_near, float dt_gamma, float bound, uint32_t H, int capacity, float* table, int* n_out,
+                                    int n_targets, const float* starts, const float* targets, float far, float* landed, int32_t* lds) {
+  if (!table || !n_out || capacity < 0 || capacity > STEP_TABLE_CAPACITY || n_targets < 0 || (n_targets > 0 && (!starts || !targets || !landed)))
+    return fail(NRF_E_INVALID, "bad argument");
+  const int n = step_table(min_near, dt_gamma, bound, H, capacity, table);
+  *n_out = n;
+  const float dt_min = step_dt_min(), dt_max = step_dt_max(bound, H);
+  for (int i = 0; i < n_targets; ++i)
+    landed[i] = step_land(n > 0 ? table : nullptr, n, starts[i], far <= 3.402823466e+38f ? fminf(targets[i], far) : targets[i], dt_gamma, dt_min, dt_max);
+  if (lds) lds[3] = step_table_lds_offset((uint32_t)lds[0], lds[1], (uint32_t)lds[2]);
+  return NRF_OK;
+}
+
+// Diagnostic (not part of include/nerfhip.h): what a render call of this context would hand the persistent kernel under its current
+// options -- out[0] = entries of the step table (0: none), out[1] = its byte offset in the workgroup's LDS (-1: not staged -- no
+// table, it does not fit, or the model has no persistent form), out[2] = the launch's LDS bytes with it.  tests/test_step_table_gpu.py.
+extern "C" int nrf_debug_step_table_launch(nrf_context* c, int32_t out[3]) {
+  int rc = need_model(c);
+  if (rc) return rc;
+  if (!out) return fail(NRF_E_INVALID, "null argument");
+  FrameParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.min_near = c->opt.min_near;
+  P.dt_gamma = c->opt.dt_gamma;
+  const float* tab = nullptr;
+  int n = 0;
+  if (!c->opt.perturb && c->march_ff) {
+    rc = step_table_for(c, P, tab, n);
+    if (rc) return rc;
+  }
+  const int lds = c->dm.persistent ? render_persistent_launch_lds_bytes(c->dm) : 0;
+  out[0] = n;
+  out[1] = c->dm.persistent && tab != nullptr ? step_table_lds_offset((uint32_t)lds, n, CU_LDS_BYTES) : -1;
+  out[2] = out[1] >= 0 ? out[1] + 4 * n : lds;
   return NRF_OK;
 }
 

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/nerfhip.h"
+#include "nrf_step_plan.h"  // NRF_STEP_TABLE, step_land: where the barrier fast-forward lands, from the launch's step table
 
 namespace nrf {
 
@@ -657,9 +658,17 @@ __device__ __forceinline__ float barrier_before(const float* ctab, int H, float 
   return e <= t_skip ? e : NONE;
 }
 
+// The launch's step table (nrf_step_plan.h) as a fast-forward sees it: the members in LDS and their number.  Null (the default:
+// the per-strip kernel, the PERTURB instances, a table that did not fit, NRF_STEP_TABLE=0): the stepping loop.
+struct StepLds {
+  const float* tab = nullptr;
+  int n = 0;
+};
+
 // mb: the mip_bound of the only level, min(1, bound)
 __device__ __forceinline__ float fast_forward_to_barrier(const MarchConst& c, const float* ctab, float mb, const float o[3], const float d[3],
-                                                         float rdx, float rdy, float rdz, float t, float t_skip, float far) {
+                                                         float rdx, float rdy, float rdz, float t, float t_skip, float far,
+                                                         const StepLds* sl = nullptr) {
   const float mag = t_skip + c.bound + 2.0f;
   const float tb = fminf(fmaxf(barrier_before(ctab, (int)c.H, mb, mag, o[0], d[0], rdx, t_skip),
                                fmaxf(barrier_before(ctab, (int)c.H, mb, mag, o[1], d[1], rdy, t_skip),
@@ -667,6 +676,10 @@ __device__ __forceinline__ float fast_forward_to_barrier(const MarchConst& c, co
   // every step below is a member before e: t < tb <= T + eps <= t_skip, and t < far as in `while (t < far ...)`
   // (an exact k-step jump -- t + k dt_max is one exact fma while t stays in its binade and dt_max is a multiple of its ulp --
   //  was built and measured: 0.4 % SLOWER than this four-instruction loop; the division and frexp per binade cost more)
+#if NRF_STEP_TABLE
+  // the persistent kernel: a ray that starts at min_near reads the member off the launch's table instead of stepping to it
+  if (sl != nullptr) return step_land(sl->tab, sl->n, t, tb, c.dt_gamma, c.dt_min, c.dt_max);
+#endif
   while (t < tb) t += clamp3(t * c.dt_gamma, c.dt_min, c.dt_max);
   return t;
 }
@@ -700,7 +713,8 @@ __device__ __forceinline__ bool cube_interval(float s, const float o[3], const f
 }
 
 __device__ __forceinline__ float fast_forward_to_barrier_pow2(const MarchConst& c, const float* ctab, const float o[3], const float d[3],
-                                                              float rdx, float rdy, float rdz, float t, float t_skip, float far) {
+                                                              float rdx, float rdy, float rdz, float t, float t_skip, float far,
+                                                              const StepLds* sl = nullptr) {
   const float NONE = -3.402823466e+38f;
   const float rd[3] = {rdx, rdy, rdz};
   const int C = (int)c.C, H = (int)c.H;
@@ -763,6 +777,9 @@ __device__ __forceinline__ float fast_forward_to_barrier_pow2(const MarchConst& 
     t_hi = nxt - 4.0f * pad;  // (well into the neighbouring shell; NONE ends the search)
   }
   const float tb = fminf(best, far);
+#if NRF_STEP_TABLE
+  if (sl != nullptr) return step_land(sl->tab, sl->n, t, tb, c.dt_gamma, c.dt_min, c.dt_max);
+#endif
   while (t < tb) t += clamp3(t * c.dt_gamma, c.dt_min, c.dt_max);
   return t;
 }

@@ -763,7 +763,7 @@ int render_strip_lds_fixed_bytes(int stage, uint32_t gen_wave_bytes) {  // the p
 }
 
 hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBatch& VBin, void* rgba, void* depth, void* counters,
-                         hipStream_t st, bool first_launch, unsigned* plan, unsigned plan_cap) {
+                         hipStream_t st, bool first_launch, unsigned* plan, unsigned plan_cap, const float* step_tab, int step_n) {
   ViewBatch VB = VBin;
   FrameParams P = Pin;
   P.plan_order = nullptr;
@@ -801,7 +801,13 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     VB.n_classes = Q.n_classes;
     VB.class_cols = Q.class_cols;
     if (Q.refused) return hipErrorInvalidValue;  // 24-bit queue positions
-    const int lds = render_persistent_launch_lds_bytes(M);
+    int lds = render_persistent_launch_lds_bytes(M);
+#if NRF_STEP_TABLE
+    // the step table goes behind everything the instance stages, when it still fits the compute unit's LDS at this wave count
+    const int step_off = step_tab != nullptr ? step_table_lds_offset((uint32_t)lds, step_n, CU_LDS_BYTES) : -1;
+    const StepArgs step = step_off >= 0 ? StepArgs{step_tab, step_n, step_off} : StepArgs{nullptr, 0, 0};
+    if (step_off >= 0) lds = step_off + 4 * step_n;
+#endif
     const int wgs = Q.workgroups;
     unsigned* queue = reinterpret_cast<unsigned*>((unsigned long long*)counters + COUNTER_SLOTS * 16);
     hipError_t e = hipSuccess;
@@ -819,7 +825,11 @@ hipError_t launch_render(const DevModel& M, const FrameParams& Pin, const ViewBa
     if (e != hipSuccess) return e;
     const int form = march_form(M.H, M.cascade, M.bound);
     const bool unit = form == MARCH_FORM_UNIT, pow2 = form == MARCH_FORM_POW2;
+#if NRF_STEP_TABLE
+    const PersistLaunch L{&M, &P, &VB, rgba, depth, counters, queue, st, lds, wgs, waves, unit, pow2, step};
+#else
     const PersistLaunch L{&M, &P, &VB, rgba, depth, counters, queue, st, lds, wgs, waves, unit, pow2};
+#endif
     if (rays) e = launch_persistent_rays(L);
     else if (M.net == NET_HOT) e = launch_persistent_hot(L);                          // the base.json shape (nrf_kernels_hot.hip)
     else if (M.net == NET_GENERIC) e = launch_persistent_generic(L);             // nrf_kernels_generic.hip

@@ -23,7 +23,7 @@ namespace nrf {
     hipError_t e_ = allow_lds(render_persistent_kernel<NET_HOT, U, WV, false, false, RAYS_DENSITY, GATHER_RUNTIME, false>, L.lds); \
     if (e_ != hipSuccess) return e_;                                                                                     \
     hipLaunchKernelGGL((render_persistent_kernel<NET_HOT, U, WV, false, false, RAYS_DENSITY, GATHER_RUNTIME, false>), dim3(L.wgs), dim3(64 * WV), \
-                       L.lds, L.st, *L.M, *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue); \
+                       L.lds, L.st, *L.M, *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue NRF_STEP_ARG(L)); \
   } while (0)
 
 hipError_t launch_persistent_rays_density(const PersistLaunch& L) {

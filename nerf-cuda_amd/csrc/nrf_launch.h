@@ -62,7 +62,8 @@ struct ViewBatch;
 constexpr int RENDER_QUEUE_BYTES = 8 * 4;
 constexpr int WIDE_GENERIC_MARCH_WAVES = 8;  // waves of the persistent workgroup of NET_WIDE with the generic march (nrf_render.h persist_waves)
 hipError_t launch_render(const DevModel& M, const FrameParams& P, const ViewBatch& VB, void* rgba, void* depth, void* counters,
-                         hipStream_t st, bool first_launch, unsigned* plan = nullptr, unsigned plan_cap = 0);
+                         hipStream_t st, bool first_launch, unsigned* plan = nullptr, unsigned plan_cap = 0,
+                         const float* step_tab = nullptr, int step_n = 0);  // the launch's step table (device; nrf_step_plan.h), null: none
 // a call's plan buffer (plan_price_kernel / plan_sort_kernel): 4 header words + a price and an order entry per queue position
 constexpr unsigned PLAN_CAP = 60u * 1024u;  // queue positions (strips) of a launch that may be planned (its last workgroup keeps a byte per position in LDS)
 constexpr size_t PLAN_BYTES = (4 + 2 * (size_t)PLAN_CAP) * 4;

@@ -1491,6 +1491,14 @@ constexpr int LDS_CLOCK_BYTES = 16;  // wave 0's entry stamps (core-clock counte
 constexpr int LDS_QUEUE_BYTES = (MAX_VIEWS + 2) * 4 + 80 + LDS_CLOCK_BYTES;  // q_begin of every view + the total; the workgroup's block counter; HelpLds; the clock stamps
 static_assert(sizeof(HelpLds) + LDS_CLOCK_BYTES <= 80 + LDS_CLOCK_BYTES, "HelpLds and the clock stamps live behind the scheduler word");
 
+// The launch's step table (nrf_step_plan.h), the LAST argument of render_persistent_kernel -- no other kernel takes it, and none of
+// the shared argument structs grows for it: tab = the members in device memory (null: no table -- it did not fit beside what the
+// instance stages, or NRF_STEP_TABLE=0 in the environment), n of them, staged at byte lds_off of the workgroup's LDS (the host
+// sized the launch for it: nrf_kernels.hip launch_render, step_table_lds_offset).
+struct StepArgs {
+  const float* tab;
+  int n, lds_off;
+};
 // The kernel's by-value arguments as they lie in the kernarg segment (the tile loop re-reads them per tile through a
 // pointer the compiler cannot see through: otherwise every field of the three structs is hoisted out of the loop and
 // kept in -- that is: spilled from -- SGPRs for the whole launch, 177 v_readlane in the march and network loops).
@@ -1498,7 +1506,15 @@ struct PersistArgs {
   DevModel M;
   FrameParams P;
   ViewBatch VB;
+#if NRF_STEP_TABLE
+  void *rgba, *depth, *counters, *queue;
+  StepArgs ST;
+#endif
 };
+#if NRF_STEP_TABLE
+static_assert(offsetof(PersistArgs, rgba) % 8 == 0 && offsetof(PersistArgs, ST) == offsetof(PersistArgs, rgba) + 32,
+              "PersistArgs mirrors the kernarg segment of render_persistent_kernel");
+#endif
 // (kernel arguments are placed like the members of a struct: each at the next multiple of its alignment)
 static_assert(offsetof(PersistArgs, P) == (sizeof(DevModel) + alignof(FrameParams) - 1) / alignof(FrameParams) * alignof(FrameParams) &&
                   offsetof(PersistArgs, VB) % alignof(ViewBatch) == 0,
@@ -1518,7 +1534,12 @@ template <int NET, int MARCH, int WAVES = persist_waves(NET), bool WLDS = false,
 __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const DevModel M0, const FrameParams P0, const ViewBatch VB0,
                                                                               float4* __restrict__ rgba0, float* __restrict__ depth0,
                                                                               unsigned long long* __restrict__ counters,
-                                                                              unsigned* __restrict__ queue) {
+                                                                              unsigned* __restrict__ queue
+#if NRF_STEP_TABLE
+                                                                              ,
+                                                                              const StepArgs ST0
+#endif
+) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = lane_id();
@@ -1548,6 +1569,12 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
   for (uint32_t i = threadIdx.x; i < M.lds_coarse_words; i += blockDim.x) coarse_lds[i] = M.occ_coarse[i];
   for (uint32_t i = threadIdx.x; i < M.lds_ctab_floats; i += blockDim.x) ctab_lds[i] = M.cell_bound[i];
   for (uint32_t i = threadIdx.x; i < M.lds_dilated_words; i += blockDim.x) dil_lds[i] = M.occ_dilated[i];
+#if NRF_STEP_TABLE
+  if (ST0.tab != nullptr) {  // the launch's step table, behind everything else (the host found the room: StepArgs)
+    float* step_lds = reinterpret_cast<float*>(smem + ST0.lds_off);
+    for (int i = (int)threadIdx.x; i < ST0.n; i += (int)blockDim.x) step_lds[i] = ST0.tab[i];
+  }
+#endif
   if constexpr (plan_levels(GP)) {  // the level table in the plan's compact form (network_from_lds is its only reader here)
     if (threadIdx.x < 16) stage_plan_level<GP>(lm.lvs, threadIdx.x, M.lv[threadIdx.x]);
   } else {
@@ -1746,9 +1773,16 @@ __global__ __launch_bounds__(64 * WAVES, 1) void render_persistent_kernel(const 
       if (any) t_skip = first;
 #if NRF_MARCH_FF
       if (any && P.march_ff != 0) {
-        if (MARCH == MARCH_UNIT) t = fast_forward_to_barrier(mc, ctab_lds, 1.0f, o, d, rdx, rdy, rdz, t, t_skip, far_m);
-        else if (MARCH == MARCH_POW2 || mc.C > 1) t = fast_forward_to_barrier_pow2(mc, ctab_lds, o, d, rdx, rdy, rdz, t, t_skip, far_m);
-        else t = fast_forward_to_barrier(mc, ctab_lds, fminf(1.0f, mc.bound), o, d, rdx, rdy, rdz, t, t_skip, far_m);
+#if NRF_STEP_TABLE
+        // (read per tile like the other arguments; a launch without a table steps: n == 0)
+        const StepLds step_tab = {ka->ST.tab != nullptr ? reinterpret_cast<const float*>(smem + ka->ST.lds_off) : nullptr, ka->ST.tab != nullptr ? ka->ST.n : 0};
+        const StepLds* sl = &step_tab;
+#else
+        const StepLds* sl = nullptr;
+#endif
+        if (MARCH == MARCH_UNIT) t = fast_forward_to_barrier(mc, ctab_lds, 1.0f, o, d, rdx, rdy, rdz, t, t_skip, far_m, sl);
+        else if (MARCH == MARCH_POW2 || mc.C > 1) t = fast_forward_to_barrier_pow2(mc, ctab_lds, o, d, rdx, rdy, rdz, t, t_skip, far_m, sl);
+        else t = fast_forward_to_barrier(mc, ctab_lds, fminf(1.0f, mc.bound), o, d, rdx, rdy, rdz, t, t_skip, far_m, sl);
       }
 #endif
     }
@@ -1961,7 +1995,15 @@ struct PersistLaunch {
   hipStream_t st;
   int lds, wgs, waves;
   bool unit, pow2;  // march form: one cascade with mip_bound 1 / several cascades with a power-of-two bound (else generic)
+#if NRF_STEP_TABLE
+  StepArgs step;    // the launch's step table (lds already holds its bytes); {nullptr, 0, 0}: none
+#endif
 };
+#if NRF_STEP_TABLE
+#define NRF_STEP_ARG(L) , (L).step
+#else
+#define NRF_STEP_ARG(L)
+#endif
 hipError_t launch_persistent_hot(const PersistLaunch& L);
 // the hot instance under a static gather plan (DevModel::gather_plan), a translation unit each: nrf_kernels_hot_qqfh.hip, ..qqhh, ..dmhh
 hipError_t launch_persistent_hot_qqfh(const PersistLaunch& L);
@@ -2009,7 +2051,7 @@ void preload_rays_hit();
     hipError_t e_ = allow_lds(render_persistent_kernel<G, U, WV, WL, O8, false, GP, FI>, L.lds);                         \
     if (e_ != hipSuccess) return e_;                                                                                     \
     hipLaunchKernelGGL((render_persistent_kernel<G, U, WV, WL, O8, false, GP, FI>), dim3(L.wgs), dim3(64 * WV), L.lds, L.st, *L.M, \
-                       *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue);         \
+                       *L.P, *L.VB, (float4*)L.rgba, (float*)L.depth, (unsigned long long*)L.counters, L.queue NRF_STEP_ARG(L)); \
   } while (0)
 #define NRF_LAUNCH_PERSISTENT_F(G, U, WV, WL, O8, FI) NRF_LAUNCH_PERSISTENT_G(G, U, WV, WL, O8, GATHER_RUNTIME, FI)
 // The hot instance under the static gather plan GP: its launcher and its code object's preload, one translation unit per plan
