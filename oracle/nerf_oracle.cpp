@@ -1,5 +1,5 @@
 // nerf_oracle.cpp -- CPU restatement of the reference hot path (see nerf_oracle.h).
-// TEST INFRASTRUCTURE ONLY; parity unpinned (no reference fixtures exist).
+// TEST INFRASTRUCTURE ONLY; rays, march and compositing are held to the reference's own kernels (ref_kernels.cpp), the network is unpinned.
 //
 // Every function cites the reference file:line it follows.  R/ = the
 // reference repo, T/ = R/dependencies/tiny-cuda-nn.
@@ -1079,6 +1079,18 @@ int nrfo_generate_rays(const nrfo_model* m, const float cam[4], const float pose
   return NRF_OK;
 }
 
+uint64_t nrfo_fnv1a(const void* data, uint64_t n) {
+  uint64_t h = 0xcbf29ce484222325ull;
+  const unsigned char* p = (const unsigned char*)data;
+  for (uint64_t i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+  return h;
+}
+
+void nrfo_near_far(const float aabb[6], const float* rays_o, const float* rays_d, uint32_t n, float min_near, float* nears,
+                   float* fars) {
+  for (uint32_t i = 0; i < n; ++i) near_far(aabb, rays_o + 3 * i, rays_d + 3 * i, min_near, nears + i, fars + i);
+}
+
 int nrfo_march(const nrfo_model* m, const nrf_options* o, const float* rays_o, const float* rays_d,
                const float* rays_t, const float* fars, uint32_t n, uint32_t n_step, float* xyzs,
                float* dirs, float* deltas) {
@@ -1196,6 +1208,22 @@ int render_impl(const nrfo_model* m, const float cam[4], const float pose[16], i
     if (per_ray_rounds) render_group(m, o, rays, true, true, 1, &n_samples, &n_rounds);
     else if (schedule == NRFO_SCHED_PER_RAY) render_rays_independent(m, o, rays, &n_samples, &n_rounds);
     else render_group(m, o, rays, true, false, 0, &n_samples, &n_rounds);
+#pragma omp parallel for schedule(static)
+    for (int py = 0; py < H; ++py)
+      for (int px = 0; px < W; ++px) finish(rays[(size_t)py * W + px], px, py);
+  } else if (schedule == NRFO_SCHED_REFERENCE_HALVES) {
+    // the NGPU = 2 build: device g owns the pixels 2 * tid + g (render_utils.h:37) and runs the loop on those N = W * H / 2 rays
+    if (((size_t)W * H) % 2 != 0) return fail(NRF_E_INVALID, "the two-device schedule needs an even number of pixels");
+    std::vector<RayState> rays((size_t)W * H);
+#pragma omp parallel for schedule(static)
+    for (int py = 0; py < H; ++py)
+      for (int px = 0; px < W; ++px) init_ray(rays[(size_t)py * W + px], px, py);
+    for (size_t g = 0; g < 2; ++g) {
+      std::vector<RayState> half(rays.size() / 2);
+      for (size_t tid = 0; tid < half.size(); ++tid) half[tid] = rays[2 * tid + g];
+      render_group(m, o, half, true, false, 0, &n_samples, &n_rounds);
+      for (size_t tid = 0; tid < half.size(); ++tid) rays[2 * tid + g] = half[tid];
+    }
 #pragma omp parallel for schedule(static)
     for (int py = 0; py < H; ++py)
       for (int px = 0; px < W; ++px) finish(rays[(size_t)py * W + px], px, py);

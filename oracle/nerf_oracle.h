@@ -6,13 +6,13 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg as the checker /
  * reported CPU baseline.
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or weights for
- * this path and cannot be built here (CUDA-only), so
- * this oracle is pinned only by the source-derived known answers of
- * SURVEY.md Appendix C (tests/test_oracle_kat.py) -- plus, where a published
- * definition exists that does not pass through this repository's reading of
- * the source, by that: scipy's spherical harmonics for the SH table, the
- * published film curves, numpy's and the CPU's fp16 conversions.
+ * PARITY: the reference ships no tests, golden vectors or weights for this path and as a whole needs CUDA.  Its ray
+ * set-up, march, compaction and compositing kernels are plain C, though: `make ref` compiles them for the CPU
+ * (ref_kernels.cpp) and tests/test_reference_kernels_cpu.py holds this oracle to them bit for bit.  The network
+ * (tcnn's encodings and fused MLP) stays pinned only by the source-derived known answers of SURVEY.md Appendix C
+ * (tests/test_oracle_kat.py) -- plus, where a published definition exists that does not pass through this
+ * repository's reading of the source, by that: scipy's spherical harmonics for the SH table, the published film
+ * curves, numpy's and the CPU's fp16 conversions.
  *
  * Arithmetic contract (what "the reference's algorithm" means here): every
  * fp32 operation individually rounded (no FMA contraction), fp16 storage with
@@ -38,6 +38,11 @@ enum {
                                n_step = clamp(N/num_alive,1,8)               */
   NRFO_SCHED_TILE64 = 1,    /* independent 8x8 pixel tiles with
                                n_step = clamp(64/alive,1,8)                  */
+  NRFO_SCHED_REFERENCE_HALVES = 3, /* the loop as the reference's NGPU = 2 build runs it (common.h:91): the pixels are
+                               dealt to two devices as pixel = 2 * tid + gpuid (render_utils.h:37) and each half runs
+                               the loop above on its own, so its step rule sees N = W * H / 2 (nerf_render.cu:243,300).
+                               W * H must be even.  NRFO_SCHED_REFERENCE is the same loop over the whole frame: the
+                               single-device program (NGPU == 1)                                                   */
   NRFO_SCHED_PER_RAY = 2    /* the reference loop with n_step == 1 for every
                                iteration (what it does whenever more than
                                half of the rays are alive): each ray is
@@ -108,6 +113,11 @@ int nrfo_network(const nrfo_model* m, const float* xyz, const float* dir, uint32
 int nrfo_generate_rays(const nrfo_model* m, const float cam[4], const float pose[16],
                        int W, int H, const nrf_options* o, float* rays_o, float* rays_d,
                        float* nears, float* fars);
+/* FNV-1a, 64 bit, over n bytes (the hash note_samples folds sample bits into): fixtures name a density grid by it */
+uint64_t nrfo_fnv1a(const void* data, uint64_t n);
+/* kernel_near_far_from_aabb (render_utils.h:338-392) on n caller-supplied rays ([n][3] each); aabb = (min xyz, max xyz) */
+void nrfo_near_far(const float aabb[6], const float* rays_o, const float* rays_d, uint32_t n, float min_near, float* nears,
+                   float* fars);
 int nrfo_march(const nrfo_model* m, const nrf_options* o, const float* rays_o,
                const float* rays_d, const float* rays_t, const float* fars, uint32_t n,
                uint32_t n_step, float* xyzs, float* dirs, float* deltas);

@@ -17,6 +17,7 @@ ORACLE_DIR = ROOT / "oracle"
 LIB = ORACLE_DIR / "libnerf_oracle.so"
 
 SCHED_REFERENCE, SCHED_TILE64, SCHED_PER_RAY = 0, 1, 2
+SCHED_REFERENCE_HALVES = 3  # the reference loop per device of its NGPU = 2 build: each half's step rule sees W * H / 2 rays
 # nrfo_set_mlp_accumulate: fp32 sums (the contract shared with the HIP path) / fp16 accumulator rounded every n products
 ACC_FP32, ACC_FP16_STEP, ACC_FP16_K4, ACC_FP16_K8, ACC_FP16_K16 = 0, 1, 4, 8, 16
 _lib = None
@@ -239,6 +240,26 @@ def composite(sigmas, rgbs, deltas, rays_t, state):
     _ck(lib().nrfo_composite(sigmas.ctypes.data, rgbs.ctypes.data, deltas.ctypes.data, n, n_step,
                              rays_t.ctypes.data, state.ctypes.data))
     return rays_t, state
+
+
+def fnv1a(a) -> int:
+    """FNV-1a (64 bit) over an array's bytes"""
+    a = np.ascontiguousarray(a)
+    L = lib()
+    L.nrfo_fnv1a.argtypes, L.nrfo_fnv1a.restype = [C.c_void_p, C.c_uint64], C.c_uint64
+    return int(L.nrfo_fnv1a(a.ctypes.data, a.nbytes))
+
+
+def near_far(aabb, rays_o, rays_d, min_near):
+    """kernel_near_far_from_aabb as the oracle states it, on caller-supplied rays [n][3]"""
+    aabb, rays_o, rays_d = _f32(aabb).reshape(6), _f32(rays_o).reshape(-1, 3), _f32(rays_d).reshape(-1, 3)
+    nears, fars = np.empty(len(rays_o), np.float32), np.empty(len(rays_o), np.float32)
+    L = lib()
+    L.nrfo_near_far.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+    L.nrfo_near_far.restype = None
+    L.nrfo_near_far(aabb.ctypes.data, rays_o.ctypes.data, rays_d.ctypes.data, len(rays_o), float(min_near), nears.ctypes.data,
+                    fars.ctypes.data)
+    return nears, fars
 
 
 def rb_accumulate(frame, accum, sample_count, color_space):
