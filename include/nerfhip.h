@@ -872,8 +872,10 @@ int nrf_composite(nrf_context* ctx, const void* sigmas, const void* rgbs,
  * on the device: bind it as the render target with
  * nrf_bind_output(ctx, rgba, depth) and the kernel composites straight into
  * it (the reference goes through host u8, main.cu:87-129).  GL / CUDA-surface
- * / DLSS / overlay parts of the reference class are out of scope; the
- * tonemapped result goes to a plain RGBA fp32 "surface" buffer.              */
+ * / image-overlay parts of the reference class are out of scope; the
+ * tonemapped result goes to a plain RGBA fp32 "surface" buffer.  Where the
+ * reference class has DLSS, nrf_rb_enable_upscale / nrf_rb_upscale (below)
+ * upscale that surface on the device.                                        */
 enum { NRF_CS_LINEAR = 0, NRF_CS_SRGB = 1, NRF_CS_VISPOSNEG = 2 };          /* EColorSpace, common.h:93-97     */
 enum { NRF_TM_IDENTITY = 0, NRF_TM_ACES = 1, NRF_TM_HABLE = 2, NRF_TM_REINHARD = 3 }; /* ETonemapCurve :100-105 */
 typedef struct nrf_render_buffer nrf_render_buffer;
@@ -905,6 +907,49 @@ int nrf_rb_overlay_depth(nrf_render_buffer* rb, float alpha, const void* depth, 
                          const float screen_center[2], void* stream);
 int nrf_rb_host_to_accumulate_buffer(nrf_render_buffer* rb, const uint8_t* rgb, int n);
 int nrf_rb_read(nrf_render_buffer* rb, float* accumulate_rgba, float* surface_rgba);  /* host copies (either may be NULL) */
+/* (ABI 7, addition) The upscaler: the developed surface at the render resolution -> a plane at an output resolution, on the device, in ONE
+ * kernel launch -- bicubic (Catmull-Rom) reconstruction with a de-ringing clamp, then a clamped unsharp mask.  It stands where the
+ * reference's render buffer has DLSS (enable_dlss / set_dlss_sharpening / in_resolution / out_resolution, dlss.png of main.cu:171-206) and
+ * is NOT DLSS: purely spatial, one frame in, no motion vectors, no depth, no history, no learned filter.  What it is instead is
+ * deterministic: every fp32 operation is ONE rounding (no contraction), every integer operation exact, no transcendental function, so a
+ * host can replay it bit for bit:
+ *   planes     the source plane P is [IH][IW] float4 (the surface), the target plane [OH][OW] float4.
+ *   geometry   per axis: r = (float)I / (float)O, computed once on the host.  For output index X: s = ((float)X + 0.5f) * r - 0.5f -- the
+ *              sum is rounded, then the product, then the difference; i = (int)floorf(s), f = s - (float)i (exact, 0 <= f < 1).  The tap
+ *              indices are i - 1, i, i + 1, i + 2, each clamped to [0, I - 1] as integers.
+ *   weights    of t = f, every operation as parenthesised: w0 = t * (-0.5f + t * (1.0f - 0.5f * t)),
+ *              w1 = 1.0f + (t * t) * (-2.5f + 1.5f * t), w2 = t * (0.5f + t * (2.0f - 1.5f * t)), w3 = (t * t) * (-0.5f + 0.5f * t).
+ *   stage 1    reconstruction, per channel, all four channels: for each of the four tap rows j,
+ *              h_j = ((wx0 * p0 + wx1 * p1) + wx2 * p2) + wx3 * p3; then v = ((wy0 * h_0 + wy1 * h_1) + wy2 * h_2) + wy3 * h_3.
+ *              De-ringing: lo and hi are the fminf / fmaxf over the four inner texels (columns i, i + 1 and rows i, i + 1, with the
+ *              clamped indices), taken as f(f(p11, p12), f(p21, p22)) row by row; U = fminf(fmaxf(v, lo), hi).
+ *   stage 2    sharpening, on the plane U at the output resolution, channels r, g, b (alpha is U's alpha): n, s, w, e are the four
+ *              neighbours of c = U[Y][X] with indices clamped to the plane; blur = ((n + s) + (w + e)) * 0.25f, d = c - blur,
+ *              x = c + amount * d, out = fminf(fmaxf(x, min(c, n, s, w, e)), max(c, n, s, w, e)), the minima and maxima nested fminf /
+ *              fmaxf from the left.
+ *   packed     rgba8 = u8(r) | u8(g) << 8 | u8(b) << 16 | u8(a) << 24 of out with the library's 8-bit rule ((unsigned char)(255.0 * x),
+ *              saturating, NaN -> 0).
+ *   it follows at equal resolutions and amount 0 the output equals the surface as values; amount 0 makes stage 2 the identity bit for
+ *              bit; a constant plane stays constant bit for bit at any ratio and amount; a 1 x 1 plane upscales to copies of its texel;
+ *              every output channel lies within the minimum and maximum of that channel over the source.
+ * nrf_rb_enable_upscale: needs a resized buffer (else NRF_E_STATE); in <= out <= 8 * in and out <= 16384 per axis (else NRF_E_INVALID and
+ *   nothing changes); the two axes may have different ratios and the ratios need not be integers.  Allocates the upscaled plane,
+ *   zero-filled; calling it again replaces the output resolution.  While it is enabled nrf_rb_resize checks the new size against the output
+ *   resolution under the same rule before anything is freed: a size that does not fit is NRF_E_INVALID and leaves the buffer as it was.
+ * nrf_rb_disable_upscale: frees the plane.  nrf_rb_upscale, nrf_rb_upscaled and nrf_rb_read_upscaled return NRF_E_STATE then, as they do
+ *   before an enable; nrf_rb_resolutions reports out == in while disabled (either array may be NULL).
+ * nrf_rb_set_upscale_sharpening: 0 <= amount <= 2 (NaN: NRF_E_INVALID); the default is 0, the value the reference's testbed sets.
+ * nrf_rb_upscale: reads the surface as the last nrf_rb_tonemap, nrf_rb_present or nrf_rb_overlay_depth left it and writes the upscaled
+ *   plane; with rgba8 != NULL also device uint32 [out_h][out_w] of the same pixels.  Stream rules are nrf_rb_present's (NULL: the
+ *   buffer's stream, and the call returns after the work has completed).  Surface, accumulate plane and spp are untouched.
+ * (csrc/nrf_upscale_plan.h is this text as code.) */
+int nrf_rb_enable_upscale(nrf_render_buffer* rb, int out_width, int out_height);  /* enable_dlss(out_res) */
+int nrf_rb_disable_upscale(nrf_render_buffer* rb);                                /* disable_dlss()       */
+int nrf_rb_set_upscale_sharpening(nrf_render_buffer* rb, float amount);           /* set_dlss_sharpening  */
+int nrf_rb_resolutions(nrf_render_buffer* rb, int in_wh[2], int out_wh[2]);       /* in_/out_resolution() */
+int nrf_rb_upscale(nrf_render_buffer* rb, void* rgba8, void* stream);
+int nrf_rb_upscaled(nrf_render_buffer* rb, void** plane);     /* device float4 [out_h][out_w] */
+int nrf_rb_read_upscaled(nrf_render_buffer* rb, float* rgba); /* host copy [out_h][out_w][4]  */
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,8 @@
 // Everything that does not depend on the pixel is settled on the host once per call: 2^exposure, the background in the
 // render colour space, the coefficients of the film curve (`FilmCurve`: identity, Reinhard, or a ratio of two quadratics --
 // ACES and Hable differ only in six numbers).  A pure stream over 16-byte pixels: one lane per pixel, grid-stride.
+// Where the reference class has DLSS (enable_dlss, set_dlss_sharpening, in_/out_resolution) this one has the upscaler: the state
+// and the entry points are here, the definition is nrf_upscale_plan.h and the kernel nrf_kernels_upscale.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "../../include/nerfhip.h"
+#include "nrf_upscale_plan.h"
 
 namespace {
 
@@ -180,6 +183,10 @@ struct nrf_render_buffer {
   uint32_t spp = 0;
   int color_space = NRF_CS_LINEAR, curve = NRF_TM_IDENTITY;
   void *frame = nullptr, *depth = nullptr, *accum = nullptr, *surface = nullptr;
+  // the upscaler (nrf_rb_enable_upscale): the output resolution (0: disabled), the sharpening amount and the plane float4 [OH][OW]
+  int OW = 0, OH = 0;
+  float sharpening = 0.0f;
+  void* upscaled = nullptr;
   hipStream_t stream = nullptr;
 };
 
@@ -191,7 +198,7 @@ int rb_fail(int code, const std::string& m) { nrf_set_last_error_(m.c_str()); re
 int rb_hip(hipError_t e, const char* what) { return rb_fail(NRF_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 #define RB_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return rb_hip(_e, #x); } while (0)
 void rb_free(nrf_render_buffer* rb) {
-  for (void** p : {&rb->frame, &rb->depth, &rb->accum, &rb->surface}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+  for (void** p : {&rb->frame, &rb->depth, &rb->accum, &rb->surface, &rb->upscaled}) { if (*p) (void)hipFree(*p); *p = nullptr; }
 }
 int rb_grid(int n) { int g = (n + 255) / 256; return g < 1 ? 1 : (g > 2048 ? 2048 : g); }
 }  // namespace
@@ -223,6 +230,9 @@ int nrf_rb_destroy(nrf_render_buffer* rb) {
 
 int nrf_rb_resize(nrf_render_buffer* rb, int width, int height) {
   if (!rb || width <= 0 || height <= 0) return rb_fail(NRF_E_INVALID, "bad resolution");
+  // with the upscaler enabled its output resolution stays: the new size has to fit it, and is checked before anything is freed
+  if (rb->OW && (!nrf::upscale_axis_valid(width, rb->OW) || !nrf::upscale_axis_valid(height, rb->OH)))
+    return rb_fail(NRF_E_INVALID, "the resolution does not fit the enabled upscale resolution (in <= out <= 8 * in per axis)");
   RB_TRY(hipSetDevice(rb->device));
   RB_TRY(hipDeviceSynchronize());
   rb_free(rb);
@@ -235,6 +245,10 @@ int nrf_rb_resize(nrf_render_buffer* rb, int width, int height) {
   RB_TRY(hipMemsetAsync(rb->depth, 0, n * 4, rb->stream));
   RB_TRY(hipMemsetAsync(rb->accum, 0, n * 16, rb->stream));
   RB_TRY(hipMemsetAsync(rb->surface, 0, n * 16, rb->stream));
+  if (rb->OW) {
+    RB_TRY(hipMalloc(&rb->upscaled, (size_t)rb->OW * rb->OH * 16));
+    RB_TRY(hipMemsetAsync(rb->upscaled, 0, (size_t)rb->OW * rb->OH * 16, rb->stream));
+  }
   RB_TRY(hipStreamSynchronize(rb->stream));
   rb->W = width;
   rb->H = height;
@@ -419,6 +433,83 @@ int nrf_rb_host_to_accumulate_buffer(nrf_render_buffer* rb, const uint8_t* rgb, 
   }
   RB_TRY(hipMemcpyAsync(rb->accum, v.data(), v.size() * 4, hipMemcpyHostToDevice, st));
   RB_TRY(hipStreamSynchronize(st));
+  return NRF_OK;
+}
+
+// ---- the upscaler: nrf_upscale_plan.h is the definition, nrf_kernels_upscale.hip the launch ----
+int nrf_rb_enable_upscale(nrf_render_buffer* rb, int out_width, int out_height) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!rb->frame) return rb_fail(NRF_E_STATE, "resize has not been called");
+  if (!nrf::upscale_axis_valid(rb->W, out_width) || !nrf::upscale_axis_valid(rb->H, out_height))
+    return rb_fail(NRF_E_INVALID, "bad upscale resolution (in <= out <= 8 * in and out <= 16384 per axis)");
+  RB_TRY(hipSetDevice(rb->device));
+  RB_TRY(hipDeviceSynchronize());
+  void* plane = nullptr;
+  const size_t bytes = (size_t)out_width * out_height * 16;
+  RB_TRY(hipMalloc(&plane, bytes));
+  hipError_t e = hipMemsetAsync(plane, 0, bytes, rb->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(rb->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(plane);
+    return rb_hip(e, "clearing the upscaled plane");
+  }
+  if (rb->upscaled) (void)hipFree(rb->upscaled);
+  rb->upscaled = plane;
+  rb->OW = out_width;
+  rb->OH = out_height;
+  return NRF_OK;
+}
+
+int nrf_rb_disable_upscale(nrf_render_buffer* rb) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (rb->upscaled) {
+    RB_TRY(hipSetDevice(rb->device));
+    RB_TRY(hipDeviceSynchronize());
+    (void)hipFree(rb->upscaled);
+  }
+  rb->upscaled = nullptr;
+  rb->OW = rb->OH = 0;
+  return NRF_OK;
+}
+
+int nrf_rb_set_upscale_sharpening(nrf_render_buffer* rb, float amount) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!nrf::upscale_amount_valid(amount)) return rb_fail(NRF_E_INVALID, "bad sharpening amount (0 <= amount <= 2)");
+  rb->sharpening = amount;
+  return NRF_OK;
+}
+
+int nrf_rb_resolutions(nrf_render_buffer* rb, int in_wh[2], int out_wh[2]) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (in_wh) in_wh[0] = rb->W, in_wh[1] = rb->H;
+  if (out_wh) out_wh[0] = rb->OW ? rb->OW : rb->W, out_wh[1] = rb->OW ? rb->OH : rb->H;
+  return NRF_OK;
+}
+
+int nrf_rb_upscale(nrf_render_buffer* rb, void* rgba8, void* stream) {
+  RB_READY();
+  (void)n;
+  if (!rb->upscaled) return rb_fail(NRF_E_STATE, "upscaling is not enabled");
+  nrf::UpscalePlan P;
+  if (!nrf::upscale_plan(rb->W, rb->H, rb->OW, rb->OH, rb->sharpening, P)) return rb_fail(NRF_E_STATE, "the resolutions do not fit");
+  RB_TRY((hipError_t)nrf::launch_upscale(P, rb->surface, rb->upscaled, rgba8, st));
+  if (!stream) RB_TRY(hipStreamSynchronize(st));
+  return NRF_OK;
+}
+
+int nrf_rb_upscaled(nrf_render_buffer* rb, void** plane) {
+  if (!rb || !plane) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!rb->upscaled) return rb_fail(NRF_E_STATE, "upscaling is not enabled");
+  *plane = rb->upscaled;
+  return NRF_OK;
+}
+
+int nrf_rb_read_upscaled(nrf_render_buffer* rb, float* rgba) {
+  if (!rb || !rgba) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!rb->upscaled) return rb_fail(NRF_E_STATE, "upscaling is not enabled");
+  RB_TRY(hipSetDevice(rb->device));
+  RB_TRY(hipDeviceSynchronize());
+  RB_TRY(hipMemcpy(rgba, rb->upscaled, (size_t)rb->OW * rb->OH * 16, hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

@@ -1,8 +1,9 @@
 // render_buffer.h -- C++ mirror of the reference's ngp::CudaRenderBuffer presentation API
 // (include/nerf-cuda/render_buffer.h:160-315) on the C ABI: same method names for resize,
 // reset_accumulation, spp, frame/depth/accumulate buffers, clear_frame, accumulate, tonemap,
-// host_to_accumulate_buffer, accumulate_buffer_host, overlay_depth.  GL textures, CUDA surfaces, DLSS and the
-// image / false-colour overlays of the reference class are out of scope (NVIDIA/GL presentation, training views).
+// host_to_accumulate_buffer, accumulate_buffer_host, overlay_depth; enable_upscale / set_upscale_sharpening / upscale stand where the
+// reference has DLSS (a proprietary binary: the deterministic spatial upscaler of nrf_rb_upscale instead).  GL textures, CUDA surfaces and
+// the image / false-colour overlays of the reference class are out of scope (NVIDIA/GL presentation, training views).
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -24,8 +25,23 @@ class RenderBuffer {
   RenderBuffer& operator=(const RenderBuffer&) = delete;
 
   void resize(const Vector2i& res) { ok(nrf_rb_resize(m_rb, res[0], res[1])); m_res = res; }
-  Vector2i in_resolution() const { return m_res; }
-  Vector2i out_resolution() const { return m_res; }
+  Vector2i in_resolution() const { int i[2] = {0, 0}; ok(nrf_rb_resolutions(m_rb, i, nullptr)); return Vector2i(i[0], i[1]); }
+  Vector2i out_resolution() const { int o[2] = {0, 0}; ok(nrf_rb_resolutions(m_rb, nullptr, o)); return Vector2i(o[0], o[1]); }
+  // The upscaler, where the reference class has enable_dlss / disable_dlss / set_dlss_sharpening: a spatial bicubic reconstruction with
+  // a clamped unsharp mask in one launch (nrf_rb_upscale), from the surface as it is to a plane of out_resolution().  Not DLSS: one
+  // frame in, no motion vectors, no depth, and a host can replay it bit for bit (include/nerfhip.h).
+  void enable_upscale(const Vector2i& out_res) { ok(nrf_rb_enable_upscale(m_rb, out_res[0], out_res[1])); }
+  void disable_upscale() { ok(nrf_rb_disable_upscale(m_rb)); }
+  void set_upscale_sharpening(float amount) { ok(nrf_rb_set_upscale_sharpening(m_rb, amount)); }
+  // rgba8: optional device uint32 [out_h][out_w]
+  void upscale(void* rgba8 = nullptr, void* stream = nullptr) { ok(nrf_rb_upscale(m_rb, rgba8, stream)); }
+  void* upscaled() const { void* p = nullptr; ok(nrf_rb_upscaled(m_rb, &p)); return p; }
+  std::vector<float> upscaled_host() {
+    const Vector2i out = out_resolution();
+    std::vector<float> v((size_t)out[0] * out[1] * 4);
+    ok(nrf_rb_read_upscaled(m_rb, v.data()));
+    return v;
+  }
   void reset_accumulation() { ok(nrf_rb_reset_accumulation(m_rb)); }
   uint32_t spp() const { uint32_t v = 0; ok(nrf_rb_spp(m_rb, &v)); return v; }
   void set_color_space(EColorSpace cs) { ok(nrf_rb_set_color_space(m_rb, (int)cs)); }

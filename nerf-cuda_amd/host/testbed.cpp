@@ -18,11 +18,19 @@
 //   of the attributes, the colours of the network are baked on the device into a per-triangle texture atlas of R (2 .. 256) texels along
 //   a triangle's legs and W (default 4096) texels width (NerfRender::bake_mesh_texture), and the mesh is written as FILE.obj with
 //   FILE.mtl and FILE.png next to it (save_obj_textured)
+//   [--upscale S [--upscale_sharpening A]] -- where the reference hands the frame to DLSS at twice the resolution and writes dlss.png
+//   (main.cu:171-206): after tonemapped.png the same render buffer upscales its surface on the device to round(W S) x round(H S),
+//   1 <= S <= 8 (the reference's fixed value is 2), sharpened by A (0 .. 2, default 0, the value the reference sets), and upscaled.png is
+//   written (RenderBuffer::enable_upscale, upscale: a deterministic spatial filter, not DLSS)
+#include <dlfcn.h>
+
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <stdexcept>
 #include <string>
 
 #include "nerf_render.h"
@@ -32,6 +40,59 @@
 constexpr size_t PATH_BATCH_VIEWS = 32;  // frames of a camera path rendered (and held) per launch
 
 using namespace ngp;
+
+// A stream and a pair of events of the HIP runtime that libnerfhip.so has loaded, looked up by name: this directory compiles
+// without HIP headers.  elapsed_ms() is the device time of what was enqueued on stream() between start() and stop().
+class DeviceTimer {
+ public:
+  DeviceTimer() {
+    create_stream = sym<int (*)(void**)>("hipStreamCreate");
+    destroy_stream = sym<int (*)(void*)>("hipStreamDestroy");
+    create_event = sym<int (*)(void**)>("hipEventCreate");
+    destroy_event = sym<int (*)(void*)>("hipEventDestroy");
+    record = sym<int (*)(void*, void*)>("hipEventRecord");
+    synchronize = sym<int (*)(void*)>("hipEventSynchronize");
+    elapsed = sym<int (*)(float*, void*, void*)>("hipEventElapsedTime");
+    ok(create_stream(&m_stream));
+    ok(create_event(&m_begin));
+    ok(create_event(&m_end));
+  }
+  ~DeviceTimer() {
+    if (m_begin) destroy_event(m_begin);
+    if (m_end) destroy_event(m_end);
+    if (m_stream) destroy_stream(m_stream);
+  }
+  DeviceTimer(const DeviceTimer&) = delete;
+  DeviceTimer& operator=(const DeviceTimer&) = delete;
+  void* stream() const { return m_stream; }
+  void start() { ok(record(m_begin, m_stream)); }
+  float stop() {
+    float ms = 0.f;
+    ok(record(m_end, m_stream));
+    ok(synchronize(m_end));
+    ok(elapsed(&ms, m_begin, m_end));
+    return ms;
+  }
+
+ private:
+  template <class F>
+  static F sym(const char* name) {
+    void* p = dlsym(RTLD_DEFAULT, name);
+    if (!p) throw std::runtime_error{std::string("the HIP runtime has no ") + name};
+    return reinterpret_cast<F>(p);
+  }
+  static void ok(int rc) {
+    if (rc != 0) throw std::runtime_error{"HIP runtime error " + std::to_string(rc) + " while timing"};
+  }
+  int (*create_stream)(void**) = nullptr;
+  int (*destroy_stream)(void*) = nullptr;
+  int (*create_event)(void**) = nullptr;
+  int (*destroy_event)(void*) = nullptr;
+  int (*record)(void*, void*) = nullptr;
+  int (*synchronize)(void*) = nullptr;
+  int (*elapsed)(float*, void*, void*) = nullptr;
+  void *m_stream = nullptr, *m_begin = nullptr, *m_end = nullptr;
+};
 
 int main(int argc, char** argv) {
   std::cout << "Hello, Metavese!" << std::endl;
@@ -44,14 +105,17 @@ int main(int argc, char** argv) {
   int mesh_refine = -1;  // (off)
   int mesh_simplify = 0;  // (off)
   int mesh_texture = 0, mesh_texture_width = 4096;  // (off)
+  float upscale = 0.0f, upscale_sharpening = 0.0f;  // (off)
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
       if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine" ||
-           a == "--mesh_simplify" || a == "--mesh_texture" || a == "--mesh_texture_width") &&
+           a == "--mesh_simplify" || a == "--mesh_texture" || a == "--mesh_texture_width" || a == "--upscale" || a == "--upscale_sharpening") &&
           i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
+        else if (a == "--upscale") upscale = (float)std::atof(argv[++i]);
+        else if (a == "--upscale_sharpening") upscale_sharpening = (float)std::atof(argv[++i]);
         else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
         else if (a == "--mesh_refine") mesh_refine = std::atoi(argv[++i]);
         else if (a == "--mesh_simplify") mesh_simplify = std::atoi(argv[++i]);
@@ -106,6 +170,27 @@ int main(int argc, char** argv) {
           out[i * 3 + j] = (unsigned char)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
         }
       pnglite::write((prefix + "tonemapped.png").c_str(), img.W, img.H, 3, out.data());
+      if (upscale != 0.0f) {
+        // main.cu:171-206 hands the frame to DLSS at out_resolution = 2 x in_resolution and writes dlss.png; here the surface just
+        // developed goes through the upscaler on the device, on a stream of this program's so that a pair of events times the launch
+        const Vector2i out_res((int)std::lround((double)img.W * upscale), (int)std::lround((double)img.H * upscale));
+        rb.enable_upscale(out_res);
+        rb.set_upscale_sharpening(upscale_sharpening);
+        DeviceTimer timer;
+        timer.start();
+        rb.upscale(nullptr, timer.stream());
+        const float ms = timer.stop();
+        const Vector2i in = rb.in_resolution(), got = rb.out_resolution();
+        std::printf("upscale: %d x %d -> %d x %d, sharpening %g, device time %.3f ms\n", in[0], in[1], got[0], got[1], upscale_sharpening, ms);
+        const std::vector<float> up = rb.upscaled_host();
+        std::vector<unsigned char> up8((size_t)got[0] * got[1] * 3);
+        for (size_t i = 0; i < (size_t)got[0] * got[1]; ++i)
+          for (int j = 0; j < 3; ++j) {
+            const float v = up[i * 4 + j] * 255;
+            up8[i * 3 + j] = (unsigned char)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
+          }
+        pnglite::write((prefix + "upscaled.png").c_str(), got[0], got[1], 3, up8.data());
+      }
     }
     FILE* f = std::fopen((prefix + "image.rgb").c_str(), "wb");  // raw copy for the parity test
     if (f) { std::fwrite(img.rgb, 1, (size_t)img.W * img.H * 3, f); std::fclose(f); }

@@ -349,6 +349,13 @@ _SIGS = {
                                        C.POINTER(C.c_float), C.c_void_p]),
     "nrf_rb_host_to_accumulate_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "nrf_rb_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_rb_enable_upscale": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "nrf_rb_disable_upscale": (C.c_int, [C.c_void_p]),
+    "nrf_rb_set_upscale_sharpening": (C.c_int, [C.c_void_p, C.c_float]),
+    "nrf_rb_resolutions": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nrf_rb_upscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_rb_upscaled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nrf_rb_read_upscaled": (C.c_int, [C.c_void_p, C.c_void_p]),
     "nrf_encode_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nrf_encode_dir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nrf_mlp_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -1342,6 +1349,38 @@ class RenderBuffer:
         sur = np.empty((self.height, self.width, 4), np.float32)
         _check(self.lib.nrf_rb_read(self.h, acc.ctypes.data, sur.ctypes.data))
         return acc, sur
+
+    # the upscaler: where the reference's render buffer has DLSS (enable_dlss, set_dlss_sharpening, in_/out_resolution); a spatial
+    # bicubic reconstruction and a clamped unsharp mask in one launch, defined in include/nerfhip.h so that a host replays it
+    def enable_upscale(self, out_width, out_height):
+        _check(self.lib.nrf_rb_enable_upscale(self.h, out_width, out_height))
+
+    def disable_upscale(self):
+        _check(self.lib.nrf_rb_disable_upscale(self.h))
+
+    def set_upscale_sharpening(self, amount):
+        _check(self.lib.nrf_rb_set_upscale_sharpening(self.h, C.c_float(amount)))
+
+    def resolutions(self):
+        """((in_width, in_height), (out_width, out_height)); out == in while upscaling is disabled"""
+        i, o = (C.c_int * 2)(), (C.c_int * 2)()
+        _check(self.lib.nrf_rb_resolutions(self.h, i, o))
+        return (int(i[0]), int(i[1])), (int(o[0]), int(o[1]))
+
+    def upscale(self, rgba8_ptr=None, stream=None):
+        """the surface as it is -> the upscaled plane (nrf_rb_upscale); rgba8_ptr: optional device uint32 [out_h][out_w]."""
+        _check(self.lib.nrf_rb_upscale(self.h, C.c_void_p(rgba8_ptr or 0), C.c_void_p(stream or 0)))
+
+    def upscaled_ptr(self):
+        p = C.c_void_p()
+        _check(self.lib.nrf_rb_upscaled(self.h, C.byref(p)))
+        return p.value
+
+    def read_upscaled(self):
+        (_, _), (ow, oh) = self.resolutions()
+        out = np.empty((oh, ow, 4), np.float32)
+        _check(self.lib.nrf_rb_read_upscaled(self.h, out.ctypes.data))
+        return out
 
 
 # --------------------------------------------------------------------------
