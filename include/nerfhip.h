@@ -950,6 +950,79 @@ int nrf_rb_resolutions(nrf_render_buffer* rb, int in_wh[2], int out_wh[2]);     
 int nrf_rb_upscale(nrf_render_buffer* rb, void* rgba8, void* stream);
 int nrf_rb_upscaled(nrf_render_buffer* rb, void** plane);     /* device float4 [out_h][out_w] */
 int nrf_rb_read_upscaled(nrf_render_buffer* rb, float* rgba); /* host copy [out_h][out_w][4]  */
+/* (ABI 7, addition) The temporal upscaler: an accumulator at the output resolution over a sequence of jittered frames at the render
+ * resolution -- how the reference drives DLSS (a per-frame sub-pixel jitter, a reset flag on sample 0, depth and motion vectors;
+ * render_buffer.cu:636-653, main.cu:53-85).  A NeRF is a static scene, so every motion vector follows from the two cameras and the depth
+ * the renderer has (the motion vectors, below).  Still no learned filter, and moving scene content is not handled.  Like the
+ * spatial upscaler it is defined operation by operation: every fp32 operation is ONE rounding, division is the correctly rounded IEEE
+ * one, integer arithmetic is exact, no transcendental function.
+ *   planes     P [IH][IW] float4 is the surface.  The history colour H [OH][OW] float4 (never sharpened) and the history weight Wt
+ *              [OH][OW] float exist twice, previous and current, swapped after each call.  The presented plane is the upscaled plane.
+ *   jitter     j = (jx, jy), each finite and in [-0.5, 0.5]: the sample of render pixel (x, y) was taken at (x + 0.5 + jx, y + 0.5 + jy)
+ *              in render pixels.  A pinhole frame gets that by rendering with cam = (fl_x, fl_y, cx - jx, cy - jy).
+ *   source     per axis: s = the spatial upscaler's s - j (one more rounded subtraction), i = (int)floorf(s), f = s - (float)i (rounded: it
+ *              may reach 1).  Taps and weights as in the spatial upscaler, of i and f.
+ *   current    C = stage 1 of the spatial upscaler (de-ringing included) at this s.  With j = (0, 0) it is its U bit for bit.
+ *   weight     per axis: n = clamp((int)floorf(s + 0.5f), 0, I - 1), d = (s - (float)n) * o with o = (float)O / (float)I from the host;
+ *              a = dx * dx + dy * dy, b = fmaxf(1.0f - a, 0.0f), wc = fmaxf(b * b, 0.015625f).
+ *   history    motion is a float2 [IH][IW] plane in OUTPUT pixels, or NULL; the vector m of output pixel (X, Y) is the entry of render
+ *              pixel (nx, ny) above; q = ((float)X + mx, (float)Y + my).  motion NULL or m exactly (0, 0): Hq and Wq are the previous
+ *              planes' texels at (X, Y), no arithmetic.  Otherwise, if m is finite and -0.5 <= q_c <= (float)O_c - 0.5f on both axes: Hq is
+ *              stage 1 (de-ringing included) on the previous H at base (int)floorf(q_c) and fraction q_c - floorf(q_c), indices clamped
+ *              to the plane; Wq is the previous Wt at clamp((int)floorf(q_c + 0.5f), 0, O_c - 1).  In every other case Wq = 0.
+ *              NRF_UPSCALE_T_RESET makes Wq = 0 everywhere and reads no history.
+ *   rectify    only with NRF_UPSCALE_T_RECTIFY and only where history is blended: per channel Hq = fminf(fmaxf(Hq, lo), hi); lo / hi are
+ *              fminf / fmaxf nested from the left over the 3 x 3 render texels around (nx, ny) in row-major order, indices clamped.
+ *              From a static camera it costs several dB, because it cuts off exactly the detail between samples: it is for moving cameras.
+ *   blend      wh = fminf(Wq, max_history).  wh > 0: tot = wh + wc, alpha = wc / tot, H' = Hq + alpha * (C - Hq) per channel (all four),
+ *              Wt' = tot.  Otherwise (reset, no history, NaN): H' = C, Wt' = wc.
+ *   presented  stage 2 of the spatial upscaler (the buffer's sharpening amount) on the plane H', and the packed pixel if asked.
+ *   sequence   jitter_k = (halton2(k + 1) - 0.5f, halton3(k + 1) - 0.5f) with the reference's recurrence: f = 1, r = 0; while i > 0:
+ *              f = f / base, r = r + f * (float)(i % base), i /= base.  (The reference keeps this Halton variant commented out beside its
+ *              scrambled Sobol sequence; that one needs the reference's direction tables and is not restated.)
+ *   motion     of a render pixel: each of the two cameras is a pose in ngp form (rotation R and centre c, exactly as the render call
+ *              converts a pose, with the loaded model's scale; 1 while none is loaded) and cam = (fl_x, fl_y, cx, cy).  For a point x:
+ *              v = x - c, p_k = (R[0][k] * v_0 + R[1][k] * v_1) + R[2][k] * v_2; p_z not finite or <= 0: invalid; else
+ *              u = (p_x / p_z) * fl_x + cx, w = (p_y / p_z) * fl_y + cy.  x = o + t * d (the product rounded, then the sum) with
+ *              t = depth / alpha where alpha >= min_alpha and t is finite and > 0; otherwise the pixel is at infinity: v = d for both
+ *              cameras.  m = ((u_prev - u_cur) * ox, (w_prev - w_cur) * oy); either projection invalid or the ray not finite:
+ *              m = (+inf, +inf), which the fetch above reads as no history.  Both projections go through the unjittered cameras.
+ * The jitter call is host only.  The history length is 1 <= max_history <= 256 (NaN: NRF_E_INVALID), default 64.
+ * The temporal call needs an enabled upscale (else NRF_E_STATE).  The four history planes are allocated, zero-filled, by the first call
+ *   and freed by nrf_rb_disable_upscale; nrf_rb_enable_upscale and nrf_rb_resize drop them, and the next call then behaves as a reset with
+ *   n_frames restarting at 0, as the first call ever does whatever the flag says.  NRF_E_INVALID with nothing written: a jitter that is not
+ *   finite or outside [-0.5, 0.5], an unknown flag, reserved != 0.  Stream rules are nrf_rb_upscale's.  nrf_rb_upscale between two temporal
+ *   calls overwrites the presented plane only.  A buffer that never makes the temporal call allocates nothing for it.
+ * The history calls return the planes the last temporal call wrote (device pointers, NULL before the first; the host copy returns
+ *   NRF_E_STATE then) and the number of calls since the history began.
+ * The motion call takes the row-major planes of a NRF_RAYS_DEPTH_T ray frame (rgba for alpha, depth_t for the sum of w t) and the rays
+ *   that made it (the jittered ones will do), writes float2 [height][width]; it needs no model, takes no slot of the calls in flight and
+ *   leaves the statistics alone.  NRF_E_INVALID: NULL pointers, resolutions outside in <= out <= 8 * in, out <= 16384, a min_alpha that is
+ *   not in (0, 1], reserved != 0.
+ * (csrc/nrf_temporal_plan.h is this text as code.) */
+enum { NRF_UPSCALE_T_RESET = 1, NRF_UPSCALE_T_RECTIFY = 2 };
+typedef struct nrf_upscale_temporal {
+  const void* motion;   /* device float2 [in_h][in_w] in output pixels, or NULL */
+  float jitter[2];
+  uint32_t flags;       /* NRF_UPSCALE_T_* */
+  uint32_t reserved;    /* 0 */
+} nrf_upscale_temporal;
+int nrf_rb_upscale_jitter(uint32_t index, float jitter[2]);                 /* host only */
+int nrf_rb_set_upscale_history(nrf_render_buffer* rb, float max_history);   /* 1..256, default 64; NaN invalid */
+int nrf_rb_upscale_temporal(nrf_render_buffer* rb, const nrf_upscale_temporal* t, void* rgba8, void* stream);
+int nrf_rb_upscale_history(nrf_render_buffer* rb, void** history, void** weight, uint32_t* n_frames);
+int nrf_rb_read_upscale_history(nrf_render_buffer* rb, float* rgba, float* weight);
+typedef struct nrf_motion {
+  const void* rays_o;   /* device float [height][width][3] */
+  const void* rays_d;   /* device float [height][width][3] */
+  const void* rgba;     /* device float4 [height][width]: alpha in w */
+  const void* depth_t;  /* device float [height][width]: the sum of w t */
+  int32_t width, height, out_width, out_height;
+  float min_alpha;
+  float cam[4], pose[16], prev_cam[4], prev_pose[16];
+  uint32_t reserved;    /* 0 */
+} nrf_motion;
+int nrf_motion_vectors(nrf_context* ctx, const nrf_motion* m, void* motion_f32x2, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@
 #include "nrf_simplify_plan.h"
 #include "nrf_model_plan.h"
 #include "nrf_points_plan.h"
+#include "nrf_temporal_plan.h"
 
 using namespace nrf;
 
@@ -2524,6 +2525,27 @@ int nrf_generate_rays_host(nrf_context* c, const float cam[4], const float pose[
   (void)hipFree(buf);
   if (rc) return rc;
   if (e != hipSuccess) return hip_fail(e, "hipMemcpy");
+  return NRF_OK;
+}
+
+// The motion vectors of a static scene (nrf_temporal_plan.h: motion_vector; nrf_kernels_temporal.hip: motion_kernel).  Both poses go
+// through motion_camera (nerf_matrix_to_ngp's operations) with the loaded model's scale, as nrf_render's do (1 while no model is loaded).  No model is needed, no slot
+// of the calls in flight is taken and the statistics are left alone.
+int nrf_motion_vectors(nrf_context* c, const nrf_motion* m, void* motion_f32x2, void* stream) {
+  if (!c) return fail(NRF_E_INVALID, "null context");
+  if (!m || !motion_f32x2 || !m->rays_o || !m->rays_d || !m->rgba || !m->depth_t) return fail(NRF_E_INVALID, "null argument");
+  if (m->reserved != 0) return fail(NRF_E_INVALID, "reserved field set");
+  MotionPlan M;
+  if (!motion_plan(m->width, m->height, m->out_width, m->out_height, m->min_alpha, M))
+    return fail(NRF_E_INVALID, "bad resolutions (in <= out <= 8 * in and out <= 16384 per axis) or min_alpha not in (0, 1]");
+  int rc = set_device(c);
+  if (rc) return rc;
+  const float scale = c->model_loaded ? c->desc.scale : 1.0f;
+  motion_camera(m->pose, scale, m->cam, M.cur);
+  motion_camera(m->prev_pose, scale, m->prev_cam, M.prev);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY((hipError_t)launch_motion(M, m->rays_o, m->rays_d, m->rgba, m->depth_t, motion_f32x2, st));
+  if (!stream) HIP_TRY(hipStreamSynchronize(st));
   return NRF_OK;
 }
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/nerfhip.h"
+#include "nrf_temporal_plan.h"
 #include "nrf_upscale_plan.h"
 
 namespace {
@@ -187,6 +188,12 @@ struct nrf_render_buffer {
   int OW = 0, OH = 0;
   float sharpening = 0.0f;
   void* upscaled = nullptr;
+  // the temporal upscaler (nrf_rb_upscale_temporal): the history colour and weight planes, twice each, allocated by the first call;
+  // `latest` is the pair the last call wrote, n_frames the calls since the history began (0: the next call is a reset)
+  void *history[2] = {nullptr, nullptr}, *weight[2] = {nullptr, nullptr};
+  int latest = 0;
+  uint32_t n_frames = 0;
+  float max_history = nrf::TEMPORAL_HISTORY_DEFAULT;
   hipStream_t stream = nullptr;
 };
 
@@ -197,8 +204,14 @@ namespace {
 int rb_fail(int code, const std::string& m) { nrf_set_last_error_(m.c_str()); return code; }
 int rb_hip(hipError_t e, const char* what) { return rb_fail(NRF_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 #define RB_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return rb_hip(_e, #x); } while (0)
+void rb_free_history(nrf_render_buffer* rb) {
+  for (void** p : {&rb->history[0], &rb->history[1], &rb->weight[0], &rb->weight[1]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+  rb->latest = 0;
+  rb->n_frames = 0;
+}
 void rb_free(nrf_render_buffer* rb) {
   for (void** p : {&rb->frame, &rb->depth, &rb->accum, &rb->surface, &rb->upscaled}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+  rb_free_history(rb);
 }
 int rb_grid(int n) { int g = (n + 255) / 256; return g < 1 ? 1 : (g > 2048 ? 2048 : g); }
 }  // namespace
@@ -454,6 +467,7 @@ int nrf_rb_enable_upscale(nrf_render_buffer* rb, int out_width, int out_height) 
     return rb_hip(e, "clearing the upscaled plane");
   }
   if (rb->upscaled) (void)hipFree(rb->upscaled);
+  rb_free_history(rb);  // (the device is idle: synchronised above)
   rb->upscaled = plane;
   rb->OW = out_width;
   rb->OH = out_height;
@@ -466,6 +480,7 @@ int nrf_rb_disable_upscale(nrf_render_buffer* rb) {
     RB_TRY(hipSetDevice(rb->device));
     RB_TRY(hipDeviceSynchronize());
     (void)hipFree(rb->upscaled);
+    rb_free_history(rb);
   }
   rb->upscaled = nullptr;
   rb->OW = rb->OH = 0;
@@ -510,6 +525,84 @@ int nrf_rb_read_upscaled(nrf_render_buffer* rb, float* rgba) {
   RB_TRY(hipSetDevice(rb->device));
   RB_TRY(hipDeviceSynchronize());
   RB_TRY(hipMemcpy(rgba, rb->upscaled, (size_t)rb->OW * rb->OH * 16, hipMemcpyDeviceToHost));
+  return NRF_OK;
+}
+
+// ---- the temporal upscaler: nrf_temporal_plan.h is the definition, nrf_kernels_temporal.hip the launch ----
+int nrf_rb_upscale_jitter(uint32_t index, float jitter[2]) {
+  if (!jitter) return rb_fail(NRF_E_INVALID, "null argument");
+  float j[2];
+  nrf::temporal_jitter(index, j);
+  jitter[0] = j[0], jitter[1] = j[1];
+  return NRF_OK;
+}
+
+int nrf_rb_set_upscale_history(nrf_render_buffer* rb, float max_history) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!nrf::temporal_history_valid(max_history)) return rb_fail(NRF_E_INVALID, "bad history length (1 <= max_history <= 256)");
+  rb->max_history = max_history;
+  return NRF_OK;
+}
+
+int nrf_rb_upscale_temporal(nrf_render_buffer* rb, const nrf_upscale_temporal* t, void* rgba8, void* stream) {
+  RB_READY();
+  (void)n;
+  if (!rb->upscaled) return rb_fail(NRF_E_STATE, "upscaling is not enabled");
+  if (!t) return rb_fail(NRF_E_INVALID, "null argument");
+  if ((t->flags & ~(uint32_t)(NRF_UPSCALE_T_RESET | NRF_UPSCALE_T_RECTIFY)) || t->reserved != 0)
+    return rb_fail(NRF_E_INVALID, "unknown flag or reserved field set");
+  if (!nrf::temporal_jitter_valid(t->jitter[0]) || !nrf::temporal_jitter_valid(t->jitter[1]))
+    return rb_fail(NRF_E_INVALID, "bad jitter (finite, within [-0.5, 0.5] per axis)");
+  const size_t texels = (size_t)rb->OW * rb->OH;
+  if (!rb->history[0]) {  // the first call: the four planes, zero-filled; all or none
+    void* planes[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) {
+      const size_t bytes = texels * (k < 2 ? 16 : 4);
+      e = hipMalloc(&planes[k], bytes);
+      if (e == hipSuccess) e = hipMemsetAsync(planes[k], 0, bytes, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      for (void* p : planes) if (p) (void)hipFree(p);
+      return rb_hip(e, "allocating the history planes");
+    }
+    rb->history[0] = planes[0], rb->history[1] = planes[1], rb->weight[0] = planes[2], rb->weight[1] = planes[3];
+    rb->latest = 0;
+    rb->n_frames = 0;
+  }
+  uint32_t flags = t->flags;
+  if (rb->n_frames == 0) flags |= NRF_UPSCALE_T_RESET;  // nothing to blend with yet
+  nrf::TemporalPlan T;
+  if (!nrf::temporal_plan(rb->W, rb->H, rb->OW, rb->OH, rb->sharpening, t->jitter[0], t->jitter[1], rb->max_history, flags, T))
+    return rb_fail(NRF_E_STATE, "the resolutions do not fit");
+  const int prev = rb->latest, next = 1 - rb->latest;
+  RB_TRY((hipError_t)nrf::launch_temporal(T, rb->surface, t->motion, rb->history[prev], rb->weight[prev], rb->history[next], rb->weight[next],
+                                          rb->upscaled, rgba8, st));
+  rb->latest = next;
+  if (rb->n_frames != UINT32_MAX) ++rb->n_frames;
+  if (!stream) RB_TRY(hipStreamSynchronize(st));
+  return NRF_OK;
+}
+
+int nrf_rb_upscale_history(nrf_render_buffer* rb, void** history, void** weight, uint32_t* n_frames) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!rb->upscaled) return rb_fail(NRF_E_STATE, "upscaling is not enabled");
+  if (history) *history = rb->history[rb->latest];
+  if (weight) *weight = rb->weight[rb->latest];
+  if (n_frames) *n_frames = rb->n_frames;
+  return NRF_OK;
+}
+
+int nrf_rb_read_upscale_history(nrf_render_buffer* rb, float* rgba, float* weight) {
+  if (!rb) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!rb->upscaled) return rb_fail(NRF_E_STATE, "upscaling is not enabled");
+  if (!rb->history[0] || rb->n_frames == 0) return rb_fail(NRF_E_STATE, "no history yet (call nrf_rb_upscale_temporal)");
+  RB_TRY(hipSetDevice(rb->device));
+  RB_TRY(hipDeviceSynchronize());
+  const size_t texels = (size_t)rb->OW * rb->OH;
+  if (rgba) RB_TRY(hipMemcpy(rgba, rb->history[rb->latest], texels * 16, hipMemcpyDeviceToHost));
+  if (weight) RB_TRY(hipMemcpy(weight, rb->weight[rb->latest], texels * 4, hipMemcpyDeviceToHost));
   return NRF_OK;
 }
 

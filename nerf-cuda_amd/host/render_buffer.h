@@ -2,7 +2,8 @@
 // (include/nerf-cuda/render_buffer.h:160-315) on the C ABI: same method names for resize,
 // reset_accumulation, spp, frame/depth/accumulate buffers, clear_frame, accumulate, tonemap,
 // host_to_accumulate_buffer, accumulate_buffer_host, overlay_depth; enable_upscale / set_upscale_sharpening / upscale stand where the
-// reference has DLSS (a proprietary binary: the deterministic spatial upscaler of nrf_rb_upscale instead).  GL textures, CUDA surfaces and
+// reference has DLSS (a proprietary binary: the deterministic spatial upscaler of nrf_rb_upscale instead, and upscale_temporal, the
+// accumulator over jittered frames of nrf_rb_upscale_temporal).  GL textures, CUDA surfaces and
 // the image / false-colour overlays of the reference class are out of scope (NVIDIA/GL presentation, training views).
 #pragma once
 #include <stdexcept>
@@ -41,6 +42,28 @@ class RenderBuffer {
     std::vector<float> v((size_t)out[0] * out[1] * 4);
     ok(nrf_rb_read_upscaled(m_rb, v.data()));
     return v;
+  }
+  // The temporal upscaler, driven the way the reference drives DLSS (render_buffer.cu:636-653): a sub-pixel jitter per frame
+  // (upscale_jitter(k): render frame k with cam.cx - jitter[0], cam.cy - jitter[1]), a reset flag, optional motion vectors (device
+  // float2 [in_h][in_w] in output pixels, NerfRender-independent: nrf_motion_vectors).  An accumulator at out_resolution(), defined in
+  // include/nerfhip.h operation by operation; no learned filter
+  static void upscale_jitter(uint32_t index, float jitter[2]) { ok(nrf_rb_upscale_jitter(index, jitter)); }
+  void set_upscale_history(float max_history) { ok(nrf_rb_set_upscale_history(m_rb, max_history)); }
+  void upscale_temporal(const float jitter[2], const void* motion = nullptr, bool reset = false, bool rectify = false, void* rgba8 = nullptr,
+                        void* stream = nullptr) {
+    nrf_upscale_temporal t{};
+    t.motion = motion;
+    t.jitter[0] = jitter[0], t.jitter[1] = jitter[1];
+    t.flags = (reset ? (uint32_t)NRF_UPSCALE_T_RESET : 0u) | (rectify ? (uint32_t)NRF_UPSCALE_T_RECTIFY : 0u);
+    ok(nrf_rb_upscale_temporal(m_rb, &t, rgba8, stream));
+  }
+  uint32_t upscale_frames() const { uint32_t n = 0; ok(nrf_rb_upscale_history(m_rb, nullptr, nullptr, &n)); return n; }
+  // the history colour [out_h][out_w][4] (unsharpened) and its weight [out_h][out_w] as the last upscale_temporal left them
+  void upscale_history_host(std::vector<float>& rgba, std::vector<float>& weight) {
+    const Vector2i out = out_resolution();
+    rgba.resize((size_t)out[0] * out[1] * 4);
+    weight.resize((size_t)out[0] * out[1]);
+    ok(nrf_rb_read_upscale_history(m_rb, rgba.data(), weight.data()));
   }
   void reset_accumulation() { ok(nrf_rb_reset_accumulation(m_rb)); }
   uint32_t spp() const { uint32_t v = 0; ok(nrf_rb_spp(m_rb, &v)); return v; }

@@ -22,6 +22,10 @@
 //   (main.cu:171-206): after tonemapped.png the same render buffer upscales its surface on the device to round(W S) x round(H S),
 //   1 <= S <= 8 (the reference's fixed value is 2), sharpened by A (0 .. 2, default 0, the value the reference sets), and upscaled.png is
 //   written (RenderBuffer::enable_upscale, upscale: a deterministic spatial filter, not DLSS)
+//   [--upscale_temporal N] -- with --upscale: N frames (1 .. 256) of the same view go through the temporal upscaler instead, the way the
+//   reference drives DLSS: frame k is rendered with the sub-pixel jitter of RenderBuffer::upscale_jitter(k) (frame 0 without, as a
+//   reset), developed alone into the surface, and accumulated at the output resolution (RenderBuffer::upscale_temporal); upscaled.png
+//   is the presented plane after the last frame
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -106,16 +110,19 @@ int main(int argc, char** argv) {
   int mesh_simplify = 0;  // (off)
   int mesh_texture = 0, mesh_texture_width = 4096;  // (off)
   float upscale = 0.0f, upscale_sharpening = 0.0f;  // (off)
+  int upscale_temporal = 0;                          // (off)
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
       if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine" ||
-           a == "--mesh_simplify" || a == "--mesh_texture" || a == "--mesh_texture_width" || a == "--upscale" || a == "--upscale_sharpening") &&
+           a == "--mesh_simplify" || a == "--mesh_texture" || a == "--mesh_texture_width" || a == "--upscale" || a == "--upscale_sharpening" ||
+           a == "--upscale_temporal") &&
           i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
         else if (a == "--upscale") upscale = (float)std::atof(argv[++i]);
         else if (a == "--upscale_sharpening") upscale_sharpening = (float)std::atof(argv[++i]);
+        else if (a == "--upscale_temporal") upscale_temporal = std::atoi(argv[++i]);
         else if (a == "--mesh_res") mesh_res = std::atoi(argv[++i]);
         else if (a == "--mesh_refine") mesh_refine = std::atoi(argv[++i]);
         else if (a == "--mesh_simplify") mesh_simplify = std::atoi(argv[++i]);
@@ -177,11 +184,32 @@ int main(int argc, char** argv) {
         rb.enable_upscale(out_res);
         rb.set_upscale_sharpening(upscale_sharpening);
         DeviceTimer timer;
-        timer.start();
-        rb.upscale(nullptr, timer.stream());
-        const float ms = timer.stop();
         const Vector2i in = rb.in_resolution(), got = rb.out_resolution();
-        std::printf("upscale: %d x %d -> %d x %d, sharpening %g, device time %.3f ms\n", in[0], in[1], got[0], got[1], upscale_sharpening, ms);
+        if (upscale_temporal > 0) {
+          // the same view N times, each frame through a camera moved by that frame's sub-pixel jitter and developed alone into the
+          // surface (the chain above), then folded into the history at the output resolution; the last launch is the one timed
+          if (upscale_temporal > 256) throw std::runtime_error{"--upscale_temporal takes 1 .. 256 frames"};
+          float ms = 0.f;
+          for (int k = 0; k < upscale_temporal; ++k) {
+            float jitter[2] = {0.f, 0.f};
+            if (k > 0) RenderBuffer::upscale_jitter((uint32_t)k, jitter);
+            const Camera jittered = {cam.fl_x, cam.fl_y, cam.cx - jitter[0], cam.cy - jitter[1]};
+            const Image frame = k == 0 ? img : render->render_frame(jittered, pos);
+            rb.reset_accumulation();
+            rb.host_to_accumulate_buffer(frame.rgb, frame.W * frame.H);
+            rb.tonemap(0.0f, bg, EColorSpace::SRGB);
+            timer.start();
+            rb.upscale_temporal(jitter, nullptr, k == 0, false, nullptr, timer.stream());
+            ms = timer.stop();
+          }
+          std::printf("upscale: %d x %d -> %d x %d, sharpening %g, temporal over %u frames, device time %.3f ms\n", in[0], in[1], got[0], got[1],
+                      upscale_sharpening, rb.upscale_frames(), ms);
+        } else {
+          timer.start();
+          rb.upscale(nullptr, timer.stream());
+          const float ms = timer.stop();
+          std::printf("upscale: %d x %d -> %d x %d, sharpening %g, device time %.3f ms\n", in[0], in[1], got[0], got[1], upscale_sharpening, ms);
+        }
         const std::vector<float> up = rb.upscaled_host();
         std::vector<unsigned char> up8((size_t)got[0] * got[1] * 3);
         for (size_t i = 0; i < (size_t)got[0] * got[1]; ++i)

@@ -121,6 +121,37 @@ class HostFrame(C.Structure):
     ]
 
 
+class UpscaleTemporal(C.Structure):
+    """nrf_upscale_temporal: one call of the temporal upscaler (nrf_rb_upscale_temporal)."""
+    _fields_ = [
+        ("motion", C.c_void_p),
+        ("jitter", C.c_float * 2),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class Motion(C.Structure):
+    """nrf_motion: the planes of a NRF_RAYS_DEPTH_T ray frame, its rays and the two cameras (nrf_motion_vectors)."""
+    _fields_ = [
+        ("rays_o", C.c_void_p),
+        ("rays_d", C.c_void_p),
+        ("rgba", C.c_void_p),
+        ("depth_t", C.c_void_p),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("out_width", C.c_int32),
+        ("out_height", C.c_int32),
+        ("min_alpha", C.c_float),
+        ("cam", C.c_float * 4),
+        ("pose", C.c_float * 16),
+        ("prev_cam", C.c_float * 4),
+        ("prev_pose", C.c_float * 16),
+        ("reserved", C.c_uint32),
+    ]
+
+
+NRF_UPSCALE_T_RESET, NRF_UPSCALE_T_RECTIFY = 1, 2
 NRF_HOST_RGB_ONLY = 1
 NRF_RAYS_DEPTH_T = 1  # nrf_rays.flags: the depth plane holds the accumulated sum of w * t, not its normalised form
 NRF_RAYS_DENSITY_ONLY = 4  # nrf_rays.flags: the density network alone -- alpha and depth as without it, rgb = (1 - alpha) * background
@@ -356,6 +387,12 @@ _SIGS = {
     "nrf_rb_upscale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_rb_upscaled": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "nrf_rb_read_upscaled": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "nrf_rb_upscale_jitter": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
+    "nrf_rb_set_upscale_history": (C.c_int, [C.c_void_p, C.c_float]),
+    "nrf_rb_upscale_temporal": (C.c_int, [C.c_void_p, C.POINTER(UpscaleTemporal), C.c_void_p, C.c_void_p]),
+    "nrf_rb_upscale_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]),
+    "nrf_rb_read_upscale_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_motion_vectors": (C.c_int, [C.c_void_p, C.POINTER(Motion), C.c_void_p, C.c_void_p]),
     "nrf_encode_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nrf_encode_dir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nrf_mlp_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -436,6 +473,13 @@ def default_per_level_scale(bound: float, base_resolution: int, n_levels: int) -
     out = C.c_float()
     _check(load_library().nrf_default_per_level_scale(C.c_float(bound), base_resolution, n_levels, C.byref(out)))
     return float(out.value)
+
+
+def upscale_jitter(k: int):
+    """(jx, jy) of frame k of the temporal upscaler's jitter sequence (nrf_rb_upscale_jitter): Halton bases 2 and 3, in [-0.5, 0.5)."""
+    j = (C.c_float * 2)()
+    _check(load_library().nrf_rb_upscale_jitter(k, j))
+    return float(j[0]), float(j[1])
 
 
 # --------------------------------------------------------------------------
@@ -1087,6 +1131,20 @@ class NerfHip:
         _check(self.lib.nrf_generate_rays(self.h, _fptr(cam), _fptr(pose), C.c_void_p(rays_o), C.c_void_p(rays_d),
                                           C.c_void_p(nears), C.c_void_p(fars), C.c_void_p(stream or 0)))
 
+    def motion_vectors(self, rays_o, rays_d, rgba, depth_t, width, height, out_width, out_height, cam, pose, prev_cam, prev_pose, out,
+                       min_alpha=0.5, stream=None, reserved=0):
+        """the motion vectors of a static scene (nrf_motion_vectors): device planes of a NRF_RAYS_DEPTH_T ray frame and its rays ->
+        device float2 [height][width] in output pixels, what RenderBuffer.upscale_temporal takes as `motion`."""
+        m = Motion()
+        m.rays_o, m.rays_d, m.rgba, m.depth_t = rays_o, rays_d, rgba, depth_t
+        m.width, m.height, m.out_width, m.out_height = width, height, out_width, out_height
+        m.min_alpha, m.reserved = min_alpha, reserved
+        m.cam[:] = [float(v) for v in np.asarray(cam, np.float32).reshape(4)]
+        m.pose[:] = [float(v) for v in np.asarray(pose, np.float32).reshape(16)]
+        m.prev_cam[:] = [float(v) for v in np.asarray(prev_cam, np.float32).reshape(4)]
+        m.prev_pose[:] = [float(v) for v in np.asarray(prev_pose, np.float32).reshape(16)]
+        _check(self.lib.nrf_motion_vectors(self.h, C.byref(m), C.c_void_p(out or 0), C.c_void_p(stream or 0)))
+
     def march(self, rays_o, rays_d, rays_t, fars, n, n_step, xyzs, dirs, deltas, stream=None):
         _check(self.lib.nrf_march(self.h, C.c_void_p(rays_o), C.c_void_p(rays_d), C.c_void_p(rays_t), C.c_void_p(fars),
                                   n, n_step, C.c_void_p(xyzs), C.c_void_p(dirs), C.c_void_p(deltas),
@@ -1381,6 +1439,34 @@ class RenderBuffer:
         out = np.empty((oh, ow, 4), np.float32)
         _check(self.lib.nrf_rb_read_upscaled(self.h, out.ctypes.data))
         return out
+
+    # the temporal upscaler: an accumulator at the output resolution over jittered frames (how the reference drives DLSS: jitter, a
+    # reset flag, motion vectors), defined in include/nerfhip.h like the spatial one
+    def set_upscale_history(self, max_history):
+        _check(self.lib.nrf_rb_set_upscale_history(self.h, C.c_float(max_history)))
+
+    def upscale_temporal(self, jitter, motion=None, reset=False, rectify=False, rgba8=None, stream=None, flags=0, reserved=0):
+        """the surface as it is, sampled with `jitter`, into the history and the upscaled plane (nrf_rb_upscale_temporal); motion: optional
+        device float2 [in_h][in_w] in output pixels; rgba8: optional device uint32 [out_h][out_w]."""
+        t = UpscaleTemporal()
+        t.motion = motion or None
+        t.jitter[0], t.jitter[1] = float(jitter[0]), float(jitter[1])
+        t.flags = flags | (NRF_UPSCALE_T_RESET if reset else 0) | (NRF_UPSCALE_T_RECTIFY if rectify else 0)
+        t.reserved = reserved
+        _check(self.lib.nrf_rb_upscale_temporal(self.h, C.byref(t), C.c_void_p(rgba8 or 0), C.c_void_p(stream or 0)))
+
+    def upscale_history(self):
+        """(history device pointer, weight device pointer, n_frames) as the last upscale_temporal left them"""
+        h, w, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        _check(self.lib.nrf_rb_upscale_history(self.h, C.byref(h), C.byref(w), C.byref(n)))
+        return h.value, w.value, int(n.value)
+
+    def read_upscale_history(self):
+        """(H' float32 [out_h][out_w][4], Wt' float32 [out_h][out_w]) of the last upscale_temporal"""
+        (_, _), (ow, oh) = self.resolutions()
+        rgba, weight = np.empty((oh, ow, 4), np.float32), np.empty((oh, ow), np.float32)
+        _check(self.lib.nrf_rb_read_upscale_history(self.h, rgba.ctypes.data, weight.ctypes.data))
+        return rgba, weight
 
 
 # --------------------------------------------------------------------------
