@@ -1,5 +1,5 @@
 // nerf_oracle.cpp -- CPU restatement of the reference hot path (see nerf_oracle.h).
-// TEST INFRASTRUCTURE ONLY; rays, march and compositing are held to the reference's own kernels (ref_kernels.cpp), the network is unpinned.
+// TEST INFRASTRUCTURE ONLY; rays, march and compositing are held to the reference's own kernels (ref_kernels.cpp), the encodings and activations to tiny-cuda-nn's (ref_encodings.cpp); the MLP is unpinned.
 //
 // Every function cites the reference file:line it follows.  R/ = the
 // reference repo, T/ = R/dependencies/tiny-cuda-nn.
@@ -182,7 +182,7 @@ inline float pcg32_first_float(uint64_t initstate, uint64_t initseq) {
 
 // ---------------------------------------------------------- activations ----
 // T/include/tiny-cuda-nn/common_device.h:68-114 (warp_activation), applied to
-// an fp32 pre-activation; the caller rounds the result to fp16.
+// an fp32 pre-activation; the caller rounds the result to fp16.  (Held to warp_activation<__half> over all 2^16 inputs: tests/test_reference_encodings_cpu.py.)
 inline float logistic(float x) { return 1.0f / (1.0f + expf(-x)); }
 // tcnn's ReLU is a PRODUCT in the network's precision: `frag.x[t] * (T)((T)frag.x[t] > (T)0.0f)` with T = __half
 // (T/include/tiny-cuda-nn/common_device.h:71-76; R/include/nerf-cuda/nerf_network.h:36-37 for the sigma activation): a negative
@@ -315,7 +315,7 @@ void nrfo_nerf_matrix_to_ngp(const float p[16], float s, float o[16]) {
   o[15] = 1;
 }
 
-// T/include/tiny-cuda-nn/encodings/grid.h:81-98 for N_DIMS = 3
+// T/include/tiny-cuda-nn/encodings/grid.h:81-98 for N_DIMS = 3; held to fast_hash<3> by tests/test_reference_encodings_cpu.py::test_grid_index_and_fast_hash
 uint32_t nrfo_fast_hash3(uint32_t x, uint32_t y, uint32_t z) {
   return (x * 1u) ^ (y * 2654435761u) ^ (z * 805459861u);
 }
@@ -358,7 +358,7 @@ void nrfo_rb_overlay_depth(float* surface, int W, int H, float alpha, const floa
 
 namespace {
 
-// T/include/tiny-cuda-nn/encodings/grid.h:899-931 (ctor) and :186-190 (kernel)
+// T/include/tiny-cuda-nn/encodings/grid.h:899-931 (ctor) and :186-190 (kernel); held to the constructor through test_encode_grid_is_kernel_grid and test_grid_index_and_fast_hash of tests/test_reference_encodings_cpu.py (the library's own copy, nrf_level_table_compute: test_level_table_is_the_constructors)
 int level_table(const nrf_model_desc& d, nrf_level_table& t) {
   if (d.n_levels == 0 || d.n_levels > 16) return fail(NRF_E_UNSUPPORTED, "n_levels must be 1..16");
   t.n_levels = d.n_levels;
@@ -507,7 +507,7 @@ int nrfo_set_contract(nrfo_model* m, int on) {
   return NRF_OK;
 }
 
-// T/include/tiny-cuda-nn/encodings/grid.h:100-117
+// T/include/tiny-cuda-nn/encodings/grid.h:100-117; held to grid_index<3, F> by tests/test_reference_encodings_cpu.py::test_grid_index_and_fast_hash
 uint32_t nrfo_grid_index(const nrfo_model* m, uint32_t level, uint32_t x, uint32_t y, uint32_t z) {
   const uint32_t hashmap_size = m->lv.offset[level + 1] - m->lv.offset[level];
   const uint32_t res = m->lv.resolution[level];
@@ -526,7 +526,7 @@ uint32_t nrfo_grid_index(const nrfo_model* m, uint32_t level, uint32_t x, uint32
 namespace {
 
 // One sample of kernel_grid<half,3,F>: T/include/tiny-cuda-nn/encodings/grid.h:186-267,
-// pos_fract: T/include/tiny-cuda-nn/common_device.h:414-422, smoothstep :379-381.
+// pos_fract: T/include/tiny-cuda-nn/common_device.h:414-422, smoothstep :379-381.  Held bit for bit to that kernel + transpose_encoded_position by tests/test_reference_encodings_cpu.py::test_encode_grid_is_kernel_grid.
 void encode_grid_one(const nrfo_model* m, const float p01[3], uint16_t* out) {
   const uint32_t L = m->d.n_levels, F = m->d.n_features_per_level;
   for (uint32_t level = 0; level < L; ++level) {
@@ -576,7 +576,7 @@ void encode_grid_one(const nrfo_model* m, const float p01[3], uint16_t* out) {
 
 // kernel_sh's polynomial table, T/include/tiny-cuda-nn/encodings/spherical_harmonics.h:66-152 (degree <= 8): the
 // published real-SH formulae as that file states them, each evaluated in C++ operator order with every fp32
-// operation individually rounded.
+// operation individually rounded.  Held to kernel_sh bit for bit by tests/test_reference_encodings_cpu.py::test_encode_dir_is_the_references_kernel.
 template <typename S>
 void sh_coefficients(uint32_t degree, S x, S y, S z, ShOut* c) {
   const S xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
@@ -656,7 +656,7 @@ void sh_coefficients(uint32_t degree, S x, S y, S z, ShOut* c) {
 }
 
 // T/include/tiny-cuda-nn/encodings/spherical_harmonics.h:57-152 (degree <= 8),
-// T/include/tiny-cuda-nn/encodings/frequency.h:56-92, identity.h:64-65.
+// T/include/tiny-cuda-nn/encodings/frequency.h:56-92, identity.h:64-65.  Held to kernel_sh / frequency_encoding / identity, padding included, by tests/test_reference_encodings_cpu.py::test_encode_dir_is_the_references_kernel.
 void encode_dir_one(const nrfo_model* m, const float d01[3], uint16_t* out) {
   const nrf_model_desc& d = m->d;
   const uint32_t pad = m->dir_width - m->dir_raw;

@@ -1,7 +1,7 @@
 /*
  * cuda_on_cpu.h -- the handful of CUDA names the reference's plain-C kernels use, for a host compiler.
  *
- * TEST INFRASTRUCTURE ONLY (oracle/ref_kernels.cpp).  Written from the interfaces the kernels use, not from any CUDA or
+ * TEST INFRASTRUCTURE ONLY (oracle/ref_kernels.cpp, oracle/ref_encodings.cpp).  Written from the interfaces the kernels use, not from any CUDA or
  * tiny-cuda-nn header.  A "launch" is two nested serial loops that set blockIdx / threadIdx (ref_kernels.cpp), so there are
  * no real threads: the index variables are thread_local only so that a caller may run launches from several host threads.
  */
@@ -85,9 +85,19 @@ inline int atomicAdd(int* address, int val) {
   *address = old + val;
   return old;
 }
+inline float atomicAdd(float* address, float val) {
+  const float old = *address;
+  *address = old + val;
+  return old;
+}
 
 /* the device intrinsic's own rounding cannot be reproduced on a CPU: libm's expf stands in (tests account for it) */
 inline float __expf(float x) { return expf(x); }
+inline float __sinf(float x) { return sinf(x); }
+inline float __cosf(float x) { return cosf(x); }
+/* named by transfer functions of common_device.h that nothing here calls */
+inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }
+inline float normcdff(float x) { return 0.5f * erfcf(-x * 0.70710678118654752440f); }
 inline float __saturatef(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
 
 inline int min(int a, int b) { return b < a ? b : a; }

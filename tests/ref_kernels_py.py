@@ -345,3 +345,138 @@ def render_frame(oracle, geo, cam, pose, W, H, opts, one_device=False, log=None)
         depth, ws = interleave([parts[0][1], parts[1][1]]), interleave([parts[0][2], parts[1][2]])
         nr = interleave([h[0][2], h[1][2]])
     return image.reshape(H, W, 3), depth.reshape(H, W), ws.reshape(H, W), nr.reshape(H, W)
+
+
+# ------------------------------------------------------------------------------------------------- the encoding kernels
+# oracle/_ref/libref_encodings.so (oracle/ref_encodings.cpp): tiny-cuda-nn's kernel_grid + transpose_encoded_position, kernel_sh,
+# frequency_encoding, identity, warp_activation and the GridEncodingTemplated constructor.  T = the reference's tiny-cuda-nn.
+ENC_LIB = ROOT / "oracle" / "_ref" / "libref_encodings.so"
+TCNN = REFERENCE / "dependencies" / "tiny-cuda-nn" / "include" / "tiny-cuda-nn"
+_enc = None
+
+
+def require_encodings():
+    """As require(), for the encoding library."""
+    import pytest
+
+    if not ENC_LIB.exists():
+        if reference_tree_exists():
+            pytest.fail(f"{ENC_LIB} is missing although the reference tree {REFERENCE} exists: run `make -C oracle ref` (build() does)")
+        pytest.skip("no reference tree and no oracle/_ref/libref_encodings.so: nothing to hold the oracle's encodings to on this machine")
+    return enc_lib()
+
+
+def enc_lib():
+    global _enc
+    if _enc is not None:
+        return _enc
+    L = C.CDLL(str(ENC_LIB))
+    vp, u32, i32, f32 = C.c_void_p, C.c_uint32, C.c_int, C.c_float
+    sig = {
+        "refk_enum_value": (i32, [C.c_char_p]),
+        "refk_grid_encode": (i32, [u32, u32, u32, vp, u32, f32, i32, i32, vp, vp, vp, u32]),
+        "refk_grid_table": (i32, [u32, u32, u32, u32, f32, i32, vp, vp, vp]),
+        "refk_grid_index": (i32, [u32, i32, u32, u32, u32, vp, vp]),
+        "refk_fast_hash3": (None, [u32, vp, vp]),
+        "refk_sh": (None, [u32, u32, u32, vp, vp]),
+        "refk_frequency": (None, [u32, u32, u32, vp, vp]),
+        "refk_identity": (None, [u32, u32, f32, f32, vp, vp]),
+        "refk_activation": (None, [i32, u32, vp, vp]),
+        "refk_half_add": (None, [u32, vp, vp, vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
+    _enc = L
+    return L
+
+
+def enum_value(name):
+    v = enc_lib().refk_enum_value(name.encode())
+    assert v >= 0, name
+    return v
+
+
+# nerfhip.h's numbering (NRF_GRID_*, NRF_INTERP_*, NRF_ACT_*) -> the reference's enumerator
+GRID_TYPES = {0: "GridType::Hash", 1: "GridType::Dense", 2: "GridType::Tiled"}
+INTERPOLATIONS = {0: "InterpolationType::Linear", 1: "InterpolationType::Nearest", 2: "InterpolationType::Smoothstep"}
+ACTIVATIONS = {0: "Activation::None", 1: "Activation::ReLU", 2: "Activation::Exponential", 3: "Activation::Sigmoid",
+               4: "Activation::Squareplus", 5: "Activation::Softplus", 6: "Activation::Sine"}
+
+
+def _u32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _u16(a):
+    return np.ascontiguousarray(a, dtype=np.uint16)
+
+
+def grid_table(F, n_levels, log2_hashmap_size, base_resolution, per_level_scale, grid_type):
+    """The GridEncodingTemplated<__half, 3, F> constructor (grid.h:875-940): (offsets [L + 1], resolutions [L], n_params), or None
+    where it throws.  grid_type is nerfhip.h's number."""
+    offsets, res, n_params = np.zeros(n_levels + 1, np.uint32), np.zeros(n_levels, np.uint32), C.c_uint64()
+    rc = enc_lib().refk_grid_table(F, F * n_levels, log2_hashmap_size, base_resolution, per_level_scale, enum_value(GRID_TYPES[grid_type]),
+                                   _p(offsets), _p(res), C.addressof(n_params))
+    assert rc in (0, 1), f"refk_grid_table: {rc} (the constructor's report could not be read)"
+    return None if rc else (offsets, res, int(n_params.value))
+
+
+def grid_encode(desc, offsets, table_f16, pos01, padded):
+    """kernel_grid<__half, 3, F> + transpose_encoded_position as GridEncodingTemplated::forward_impl launches them (grid.h:942-1018):
+    uint16 [n][padded].  desc: a ModelDesc; offsets: the level offsets; table_f16: the grid's parameters as fp16 bits."""
+    pos01, offsets, table_f16 = _f32(pos01).reshape(-1, 3), _u32(offsets), _u16(table_f16)
+    F, L = int(desc.n_features_per_level), int(desc.n_levels)
+    assert len(offsets) == L + 1 and len(table_f16) == int(offsets[L]) * F
+    out = np.full((len(pos01), padded), 0xDEAD, np.uint16)
+    rc = enc_lib().refk_grid_encode(F, len(pos01), F * L, _p(offsets), int(desc.base_resolution), float(desc.per_level_scale),
+                                    enum_value(INTERPOLATIONS[int(desc.interpolation)]), enum_value(GRID_TYPES[int(desc.grid_type)]),
+                                    _p(table_f16), _p(pos01), _p(out), padded)
+    assert rc == 0
+    return out
+
+
+def grid_index(F, grid_type, hashmap_size, resolution, corners):
+    """grid_index<3, F>(.., feature 0, ..) (grid.h:100-117) over corners uint32 [n][3]: F * entry"""
+    corners = _u32(corners).reshape(-1, 3)
+    out = np.empty(len(corners), np.uint32)
+    assert enc_lib().refk_grid_index(F, enum_value(GRID_TYPES[grid_type]), int(hashmap_size), int(resolution), len(corners), _p(corners), _p(out)) == 0
+    return out
+
+
+def fast_hash3(corners):
+    corners = _u32(corners).reshape(-1, 3)
+    out = np.empty(len(corners), np.uint32)
+    enc_lib().refk_fast_hash3(len(corners), _p(corners), _p(out))
+    return out
+
+
+def encode_dir(kind, arg, dir01, padded):
+    """kernel_sh (kind 0, arg = degree), frequency_encoding (1, n_frequencies) or identity (2) as their encodings' forward_impl
+    launch them, with the padding that brings the row to `padded`: uint16 [n][padded]"""
+    dir01 = _f32(dir01).reshape(-1, 3)
+    raw = {0: arg * arg, 1: 6 * arg, 2: 3}[kind]
+    out = np.full((len(dir01), padded), 0xDEAD, np.uint16)
+    L = enc_lib()
+    if kind == 0:
+        L.refk_sh(len(dir01), arg, padded - raw, _p(dir01), _p(out))
+    elif kind == 1:
+        L.refk_frequency(len(dir01), arg, padded - raw, _p(dir01), _p(out))
+    else:
+        L.refk_identity(len(dir01), padded - raw, 1.0, 0.0, _p(dir01), _p(out))
+    return out
+
+
+def activation(act, bits):
+    """warp_activation<__half> (common_device.h:68-114) of fp16 bit patterns; act is nerfhip.h's number"""
+    bits = _u16(bits)
+    out = np.empty_like(bits)
+    enc_lib().refk_activation(enum_value(ACTIVATIONS[act]), bits.size, _p(bits), _p(out))
+    return out
+
+
+def half_add(a, b):
+    a, b = _u16(a), _u16(b)
+    out = np.empty_like(a)
+    enc_lib().refk_half_add(a.size, _p(a), _p(b), _p(out))
+    return out
