@@ -119,7 +119,7 @@ __device__ __forceinline__ float4 develop(float4 mean, const PresentArgs& A) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = fmaxf(c[k], 0.f);
     if (A.film.kind == CURVE_LUMA) {
-      const float scale = 1.f / ((0.2126f * c[0] + 0.7152f * c[1] + 0.0722f * c[2]) + 1.0f);
+      const float scale = 1.f / ((0.2126f * c[0] + (0.7152f * c[1] + 0.0722f * c[2])) + 1.0f);  // a 3-term Eigen dot: p0 + (p1 + p2)
 #pragma unroll
       for (int k = 0; k < 3; ++k) c[k] = c[k] * scale;
     } else {
@@ -377,9 +377,11 @@ int nrf_rb_present(nrf_render_buffer* rb, float exposure, const float bg[4], int
 }
 
 // overlay_depth_kernel, R/src/render_buffer.cu:431-477 with colormap_turbo (:413-429): the polynomial is evaluated
-// as the fixed-size Eigen dot products do, ((a0*b0 + a1*b1) + a2*b2) + a3*b3, every operation rounded on its own.
+// as the fixed-size Eigen dot products do.  Eigen's unrolled scalar reduction splits a sum in halves, so a 4-term dot is
+// (a0*b0 + a1*b1) + (a2*b2 + a3*b3) and a 3-term one p0 + (p1 + p2), every operation rounded on its own
+// (tests/test_reference_render_buffer_cpu.py holds the oracle's copy to the reference's own Eigen).
 __device__ __forceinline__ float dot4(const float a[4], float b0, float b1, float b2, float b3) {
-  return ((a[0] * b0 + a[1] * b1) + a[2] * b2) + a[3] * b3;
+  return (a[0] * b0 + a[1] * b1) + (a[2] * b2 + a[3] * b3);
 }
 __device__ __forceinline__ void colormap_turbo(float x, float c[3]) {
   const float kR4[4] = {0.13572138f, 4.61539260f, -42.66032258f, 132.13108234f};

@@ -321,7 +321,8 @@ uint32_t nrfo_fast_hash3(uint32_t x, uint32_t y, uint32_t z) {
 }
 
 // R/src/render_buffer.cu:413-429 (colormap_turbo) and :431-477 (overlay_depth_kernel); surface [H][W][4] in place
-static float dot4_(const float a[4], float b0, float b1, float b2, float b3) { return ((a[0] * b0 + a[1] * b1) + a[2] * b2) + a[3] * b3; }
+// Eigen's unrolled scalar reduction (redux_novec_unroller) splits in halves: a 4-term dot is (p0 + p1) + (p2 + p3)
+static float dot4_(const float a[4], float b0, float b1, float b2, float b3) { return (a[0] * b0 + a[1] * b1) + (a[2] * b2 + a[3] * b3); }
 void nrfo_rb_overlay_depth(float* surface, int W, int H, float alpha, const float* depth, float depth_scale, int img_w, int img_h,
                            int fov_axis, float zoom, float center_x, float center_y) {
   const float kR4[4] = {0.13572138f, 4.61539260f, -42.66032258f, 132.13108234f};
@@ -1404,7 +1405,7 @@ static void tonemap_curve(float c[3], int curve) {
     k0 = 4.0f * k0 * white_scale; k1 = 2.0f * k1 * white_scale; k2 = k2 * white_scale;
     k3 = 4.0f * k3; k4 = 2.0f * k4;
   } else {
-    const float Y = 0.2126f * c[0] + 0.7152f * c[1] + 0.0722f * c[2];
+    const float Y = 0.2126f * c[0] + (0.7152f * c[1] + 0.0722f * c[2]);  // a 3-term Eigen dot: p0 + (p1 + p2)
     const float s = 1.f / (Y + 1.0f);
     for (int i = 0; i < 3; ++i) c[i] = c[i] * s;
     return;
