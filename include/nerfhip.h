@@ -871,9 +871,10 @@ int nrf_composite(nrf_context* ctx, const void* sigmas, const void* rgbs,
  * :529-556 tonemap_kernel, :590-627).  The frame buffer is RGBA fp32 + depth
  * on the device: bind it as the render target with
  * nrf_bind_output(ctx, rgba, depth) and the kernel composites straight into
- * it (the reference goes through host u8, main.cu:87-129).  GL / CUDA-surface
- * / image-overlay parts of the reference class are out of scope; the
- * tonemapped result goes to a plain RGBA fp32 "surface" buffer.  Where the
+ * it (the reference goes through host u8, main.cu:87-129).  The GL / CUDA-surface
+ * parts of the reference class are out of scope; the tonemapped result goes
+ * to a plain RGBA fp32 "surface" buffer, and the class's three overlays
+ * (depth, image, false colour) blend over it (below).  Where the
  * reference class has DLSS, nrf_rb_enable_upscale / nrf_rb_upscale (below)
  * upscale that surface on the device.                                        */
 enum { NRF_CS_LINEAR = 0, NRF_CS_SRGB = 1, NRF_CS_VISPOSNEG = 2 };          /* EColorSpace, common.h:93-97     */
@@ -907,6 +908,63 @@ int nrf_rb_overlay_depth(nrf_render_buffer* rb, float alpha, const void* depth, 
                          const float screen_center[2], void* stream);
 int nrf_rb_host_to_accumulate_buffer(nrf_render_buffer* rb, const uint8_t* rgb, int n);
 int nrf_rb_read(nrf_render_buffer* rb, float* accumulate_rgba, float* surface_rgba);  /* host copies (either may be NULL) */
+/* (ABI 7, addition) The image overlay, the false-colour overlay and the error map: the two remaining public methods of the reference's
+ * CudaRenderBuffer (overlay_image, render_buffer.cu:341-411, 656-688; overlay_false_color, :479-527, 716-733) and the producer of what the
+ * second one reads.  Every fp32 operation is ONE rounding (no contraction), every integer operation exact, in the order of the
+ * reference's source text; the one transcendental function is the power inside the sRGB pair.  W x H is the surface.
+ *   pixel mapping   (nrf_rb_overlay_depth's) surface pixel (x, y) -> (srcx, srcy) of an iw x ih image:
+ *                   scale = (float)(fov_axis == 0 ? iw : ih) / (float)(fov_axis == 0 ? W : H);
+ *                   fx = (float)x + 0.5f; fx -= (float)W * 0.5f; fx /= zoom; fx += screen_center[0] * (float)W; fy likewise with H and
+ *                   screen_center[1]; u = (fx - (float)W * 0.5f) * scale + (float)iw * 0.5f; v likewise; srcx = (int)floorf(u),
+ *                   srcy = (int)floorf(v), where the conversion saturates and a NaN gives an index outside the image.
+ *   image texels    image_data_type is the reference's EImageDataType.  NRF_IMG_BYTE: uint32 texels r | g << 8 | b << 16 | a << 24, sRGB
+ *                   with straight alpha.  The texel 0x00FF00FF gives (-1, -1, -1, -1); otherwise a = (float)b3 * (1.0f / 255.0f) and
+ *                   channel = T[b] * a with T[b] = srgb_to_linear((float)b * (1.0f / 255.0f)), b = 0 .. 255, a table the library makes
+ *                   ONCE on the host with libm (nrf_rb_srgb8_table returns it) -- the one deliberate difference from evaluating the
+ *                   power per pixel on the device: a Byte image is bit-exact against a CPU compile of the reference.  NRF_IMG_HALF:
+ *                   four fp16 values per texel, widened exactly.  NRF_IMG_FLOAT: four fp32 values.  Premultiplied linear values both.
+ *   nrf_rb_overlay_image, per surface pixel: val = the texel at (srcx, srcy), zeros when that lies outside the image.  Render colour
+ *                   space sRGB: rgb = linear_to_srgb(rgb / w) * w for w > 0, else 0; otherwise the background colour (given as sRGB) is
+ *                   decoded on the host once per call, as nrf_rb_tonemap does.  weight = (1 - w) * bg.w; rgb += bg.rgb * weight;
+ *                   w += weight.  Then the reference's five-argument tonemap: srgb_to_linear if the render space is sRGB, times
+ *                   powf(2, exposure[k]) per channel (made on the host), the buffer's film curve (the curves' max(x, 0) is fmaxf), and
+ *                   linear_to_srgb if output_color_space is sRGB.  surface = color * alpha + surface * (1.f - alpha), all four channels.
+ *   nrf_rb_overlay_false_color, per surface pixel: error_map_scale = brightness / (0.0000001f + average[0]);
+ *                   scale = (float)(fov_axis == 0 ? tw : th) / (float)(fov_axis == 0 ? W : H) with tw x th the training resolution;
+ *                   u = ((float)x + 0.5f - (float)W * 0.5f) * scale + (float)tw * 0.5f, v likewise;
+ *                   srcx = (int)floorf(u * (float)map_width / fmaxf(1.f, (float)tw)), srcy likewise (the same conversion).  A pixel
+ *                   outside the map is left untouched.  err = map[srcy][srcx] * error_map_scale; with viridis err *= 1.f / (1.f + err).
+ *                   c = colormap_viridis(err) -- c0 + x (c1 + x (c2 + x (c3 + x (c4 + x (c5 + x c6))))) per channel on x clamped to
+ *                   [0, 1] -- or colormap_turbo(err), nrf_rb_overlay_depth's.  grey = r * 0.2126f + g * 0.7152f + b * 0.0722f, summed
+ *                   left to right; rgb = grey * sat(c) with sat clamping to [0, 1] and NaN -> 0; alpha untouched.  (The reference's
+ *                   to_srgb argument is dead in its kernel and is not part of this call.)
+ *   nrf_rb_error_map (this library's definition: the reference fills its map while training): the surface S against a truth plane G,
+ *                   both float4 [H][W], into a map float [map_height][map_width] with 1 <= map_width <= min(W, 512),
+ *                   1 <= map_height <= min(H, 512), and its average, one float.  Cell cx covers columns x0(cx) .. x0(cx + 1) - 1 with
+ *                   x0(c) = (c * W + map_width - 1) / map_width in integers, rows likewise: every cell holds at least one pixel.  Per
+ *                   pixel e = (((dr * dr) + (dg * dg)) + (db * db)) / 3.0f with d = S - G; alpha is ignored.  A cell is reduced in a
+ *                   fixed order: with its pixels row-major as k = 0, 1, ..., v[l] (l = 0 .. 63) adds e_k for k = l (mod 64) in
+ *                   ascending k onto 0.0f; then for s = 32, 16, ..., 1 and l < s, v[l] = v[l] + v[l + s]; the cell's value is
+ *                   v[0] / (float)count.  The average is the same scheme over the cells in row-major order:
+ *                   average[0] = v[0] / (float)(map_width * map_height).  NaNs propagate.  The average is the MEAN OF THE CELL MEANS: it
+ *                   equals the image's mean squared error only when map_width divides W and map_height divides H.
+ * image, error_map, average and truth_f32x4 are device pointers; error_map and average of nrf_rb_error_map may be handed to
+ * nrf_rb_overlay_false_color as they are, on the same stream.  Stream rules are nrf_rb_overlay_depth's (NULL: the buffer's stream, and
+ * the call returns after the work has completed).  NRF_E_STATE before a resize.  NRF_E_INVALID, with nothing written: a NULL pointer, an
+ * unknown data type or colour space, a fov_axis other than 0 or 1, an image, training or surface size <= 0 or above 16384 on an axis, map
+ * sizes outside 1 .. 512 (nrf_rb_error_map: outside the bounds above), a zoom that is zero or not finite, a screen_center that is not
+ * finite.  nrf_rb_srgb8_table is host only and needs no device.
+ * (csrc/nrf_overlay_plan.h is this text as code.) */
+enum { NRF_IMG_BYTE = 1, NRF_IMG_HALF = 2, NRF_IMG_FLOAT = 3 };              /* EImageDataType, common.h */
+int nrf_rb_srgb8_table(float table[256]);                                   /* host only */
+int nrf_rb_overlay_image(nrf_render_buffer* rb, float alpha, const float exposure[3], const float background_color[4],
+                         int output_color_space, const void* image, int image_data_type, int image_width, int image_height,
+                         int fov_axis, float zoom, const float screen_center[2], void* stream);
+int nrf_rb_overlay_false_color(nrf_render_buffer* rb, int training_width, int training_height, int fov_axis,
+                               const void* error_map, int map_width, int map_height, const void* average,
+                               float brightness, int viridis, void* stream);
+int nrf_rb_error_map(nrf_render_buffer* rb, const void* truth_f32x4, int map_width, int map_height,
+                     void* error_map, void* average, void* stream);
 /* (ABI 7, addition) The upscaler: the developed surface at the render resolution -> a plane at an output resolution, on the device, in ONE
  * kernel launch -- bicubic (Catmull-Rom) reconstruction with a de-ringing clamp, then a clamped unsharp mask.  It stands where the
  * reference's render buffer has DLSS (enable_dlss / set_dlss_sharpening / in_resolution / out_resolution, dlss.png of main.cu:171-206) and

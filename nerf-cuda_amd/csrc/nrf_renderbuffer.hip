@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/nerfhip.h"
+#include "nrf_overlay_plan.h"
 #include "nrf_temporal_plan.h"
 #include "nrf_upscale_plan.h"
 
@@ -30,47 +31,16 @@ namespace {
 thread_local std::string g_rb_err;
 extern "C" const char* nrf_last_error(void);
 
-// the sRGB transfer pair as the reference states it (R/include/nerf-cuda/common_device.cuh:38-60: note the 0.41666 exponent).
-// On the device the power is 2^(e log2 x) on the two transcendental instructions (v_log_f32, v_exp_f32; the argument is
-// positive on this branch): within 2e-6 of libm's powf over the range a colour takes -- the general powf made the chain
-// ALU-bound (32-52 us per 1080p plane against 20 us for the same stream without it, profiles/r05/rb_bench.txt).  The host
-// forms (the background colour, once per call) stay libm's, which is the oracle's.
-__host__ __device__ inline float pow_positive(float x, float e) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x));
-#else
-  return powf(x, e);
-#endif
-}
-__host__ __device__ inline float decode_srgb(float v) { return v <= 0.04045f ? v / 12.92f : pow_positive((v + 0.055f) / 1.055f, 2.4f); }
-__host__ __device__ inline float encode_srgb(float v) { return v < 0.0031308f ? 12.92f * v : 1.055f * pow_positive(v, 0.41666f) - 0.055f; }
-
-// A film curve, reduced on the host to what the pixel loop needs.  RATIONAL: y = (x^2 n2 + n1 x + n0) / (d2 x^2 + d1 x + d0)
-// on max(x, 0) per channel (operation order as written: it is part of the contract with the oracle); LUMA: Reinhard's
-// x / (1 + Y) on max(x, 0) with Y the Rec. 709 luminance.
-enum : int { CURVE_NONE = 0, CURVE_RATIONAL = 1, CURVE_LUMA = 2 };
-struct FilmCurve {
-  int kind;
-  float n2, n1, n0, d2, d1, d0;
-};
-FilmCurve film_curve(int tonemap) {  // render_buffer.cu:261-318, the constants of its two rational curves
-  FilmCurve f{CURVE_NONE, 0, 0, 0, 0, 0, 0};
-  if (tonemap == NRF_TM_ACES) {  // Narkowicz's fit, pre-scaled by 0.6
-    f = {CURVE_RATIONAL, 0.6f * 0.6f * 2.51f, 0.6f * 0.03f, 0.0f, 0.6f * 0.6f * 2.43f, 0.6f * 0.59f, 0.14f};
-  } else if (tonemap == NRF_TM_HABLE) {  // Hable's filmic operator, normalised so that the white point 11.2 maps to 1
-    const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f, white = 11.2f;
-    float n2 = A * F - A * E, n1 = C * B * F - B * E, n0 = 0.0f;
-    float d2 = A * F, d1 = B * F;
-    const float d0 = D * F * F;
-    const float at_white_n = n2 * (white * white) + n1 * white + n0;
-    const float at_white_d = d2 * (white * white) + d1 * white + d0;
-    const float norm = at_white_d / at_white_n;
-    f = {CURVE_RATIONAL, 4.0f * n2 * norm, 2.0f * n1 * norm, n0 * norm, 4.0f * d2, 2.0f * d1, d0};
-  } else if (tonemap == NRF_TM_REINHARD) {
-    f.kind = CURVE_LUMA;
-  }
-  return f;
-}
+// the sRGB pair, the film curves and the colour maps are nrf_overlay_plan.h's: one text for these kernels, the overlay kernels and the host
+using nrf::colormap_turbo;
+using nrf::decode_srgb;
+using nrf::encode_srgb;
+using nrf::film_curve;
+using nrf::FilmCurve;
+static_assert(nrf::CS_LINEAR == NRF_CS_LINEAR && nrf::CS_SRGB == NRF_CS_SRGB && nrf::CS_VISPOSNEG == NRF_CS_VISPOSNEG, "the plan's colour spaces");
+static_assert(nrf::TM_IDENTITY == NRF_TM_IDENTITY && nrf::TM_ACES == NRF_TM_ACES && nrf::TM_HABLE == NRF_TM_HABLE && nrf::TM_REINHARD == NRF_TM_REINHARD,
+              "the plan's curves");
+static_assert(nrf::IMG_BYTE == NRF_IMG_BYTE && nrf::IMG_HALF == NRF_IMG_HALF && nrf::IMG_FLOAT == NRF_IMG_FLOAT, "the plan's image data types");
 
 // one call's pixel-independent state
 struct PresentArgs {
@@ -110,33 +80,9 @@ __device__ __forceinline__ float4 develop(float4 mean, const PresentArgs& A) {
   const float uncovered = (1 - mean.w) * A.backdrop.w;
   float c[3] = {mean.x + A.backdrop.x * uncovered, mean.y + A.backdrop.y * uncovered, mean.z + A.backdrop.z * uncovered};
   const float alpha = mean.w + uncovered;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (A.render_space == NRF_CS_SRGB) c[k] = decode_srgb(c[k]);
-    c[k] *= A.gain;
-  }
-  if (A.film.kind != CURVE_NONE) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = fmaxf(c[k], 0.f);
-    if (A.film.kind == CURVE_LUMA) {
-      const float scale = 1.f / ((0.2126f * c[0] + (0.7152f * c[1] + 0.0722f * c[2])) + 1.0f);  // a 3-term Eigen dot: p0 + (p1 + p2)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) c[k] = c[k] * scale;
-    } else {
-      const FilmCurve& f = A.film;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float sq = c[k] * c[k];
-        c[k] = (sq * f.n2 + f.n1 * c[k] + f.n0) / (f.d2 * sq + f.d1 * c[k] + f.d0);
-      }
-    }
-  }
+  const float gain[3] = {A.gain, A.gain, A.gain};
+  nrf::develop_color(c, A.render_space, gain, A.film, A.display_space);
   float4 out = make_float4(c[0], c[1], c[2], alpha);
-  if (A.display_space == NRF_CS_SRGB) {
-    out.x = encode_srgb(out.x);
-    out.y = encode_srgb(out.y);
-    out.z = encode_srgb(out.z);
-  }
   if (A.clamp_display) {
     out.x = fminf(fmaxf(out.x, 0.f), 1.f);
     out.y = fminf(fmaxf(out.y, 0.f), 1.f);
@@ -194,6 +140,8 @@ struct nrf_render_buffer {
   int latest = 0;
   uint32_t n_frames = 0;
   float max_history = nrf::TEMPORAL_HISTORY_DEFAULT;
+  // the 256 floats of nrf_rb_srgb8_table on the device, made by the first nrf_rb_overlay_image of a Byte image; freed by destroy
+  void* srgb8 = nullptr;
   hipStream_t stream = nullptr;
 };
 
@@ -236,6 +184,7 @@ int nrf_rb_destroy(nrf_render_buffer* rb) {
   (void)hipSetDevice(rb->device);
   (void)hipDeviceSynchronize();
   rb_free(rb);
+  if (rb->srgb8) (void)hipFree(rb->srgb8);
   if (rb->stream) (void)hipStreamDestroy(rb->stream);
   delete rb;
   return NRF_OK;
@@ -376,29 +325,7 @@ int nrf_rb_present(nrf_render_buffer* rb, float exposure, const float bg[4], int
   return NRF_OK;
 }
 
-// overlay_depth_kernel, R/src/render_buffer.cu:431-477 with colormap_turbo (:413-429): the polynomial is evaluated
-// as the fixed-size Eigen dot products do.  Eigen's unrolled scalar reduction splits a sum in halves, so a 4-term dot is
-// (a0*b0 + a1*b1) + (a2*b2 + a3*b3) and a 3-term one p0 + (p1 + p2), every operation rounded on its own
-// (tests/test_reference_render_buffer_cpu.py holds the oracle's copy to the reference's own Eigen).
-__device__ __forceinline__ float dot4(const float a[4], float b0, float b1, float b2, float b3) {
-  return (a[0] * b0 + a[1] * b1) + (a[2] * b2 + a[3] * b3);
-}
-__device__ __forceinline__ void colormap_turbo(float x, float c[3]) {
-  const float kR4[4] = {0.13572138f, 4.61539260f, -42.66032258f, 132.13108234f};
-  const float kG4[4] = {0.09140261f, 2.19418839f, 4.84296658f, -14.18503333f};
-  const float kB4[4] = {0.10667330f, 12.64194608f, -60.58204836f, 110.36276771f};
-  const float kR2[2] = {-152.94239396f, 59.28637943f};
-  const float kG2[2] = {4.27729857f, 2.82956604f};
-  const float kB2[2] = {-89.90310912f, 27.34824973f};
-  x = fminf(fmaxf(x, 0.0f), 1.0f);  // __saturatef (NaN -> 0)
-  if (!(x == x)) x = 0.0f;
-  const float x2 = x * x, x3 = x2 * x;
-  const float v20 = x3 * x, v21 = x3 * x2;
-  c[0] = dot4(kR4, 1.0f, x, x2, x3) + (v20 * kR2[0] + v21 * kR2[1]);
-  c[1] = dot4(kG4, 1.0f, x, x2, x3) + (v20 * kG2[0] + v21 * kG2[1]);
-  c[2] = dot4(kB4, 1.0f, x, x2, x3) + (v20 * kB2[0] + v21 * kB2[1]);
-}
-
+// overlay_depth_kernel, R/src/render_buffer.cu:431-477 with colormap_turbo (:413-429, nrf_overlay_plan.h)
 __global__ __launch_bounds__(256) void overlay_depth_kernel(int W, int H, float alpha, const float* __restrict__ depth,
                                                             float depth_scale, int img_w, int img_h, int fov_axis, float zoom,
                                                             float center_x, float center_y, float4* __restrict__ surface) {
@@ -433,6 +360,92 @@ int nrf_rb_overlay_depth(nrf_render_buffer* rb, float alpha, const void* depth, 
   hipLaunchKernelGGL(overlay_depth_kernel, dim3(rb_grid(n)), dim3(256), 0, st, rb->W, rb->H, alpha, (const float*)depth, depth_scale,
                      image_width, image_height, fov_axis, zoom, screen_center[0], screen_center[1], (float4*)rb->surface);
   RB_TRY(hipGetLastError());
+  if (!stream) RB_TRY(hipStreamSynchronize(st));
+  return NRF_OK;
+}
+
+// ---- the image and false-colour overlays and the error map: nrf_overlay_plan.h is the definition, nrf_kernels_overlay.hip the launches ----
+namespace {
+const float* srgb8_table() {  // made once, on the host, with libm
+  static const struct Table {
+    float t[256];
+    Table() { nrf::overlay_srgb8_table(t); }
+  } table;
+  return table.t;
+}
+bool overlay_size_valid(int v) { return v > 0 && v <= nrf::OVERLAY_SIZE_MAX; }
+}  // namespace
+
+int nrf_rb_srgb8_table(float table[256]) {
+  if (!table) return rb_fail(NRF_E_INVALID, "null argument");
+  std::memcpy(table, srgb8_table(), 256 * sizeof(float));
+  return NRF_OK;
+}
+
+int nrf_rb_overlay_image(nrf_render_buffer* rb, float alpha, const float exposure[3], const float background_color[4], int output_color_space,
+                         const void* image, int image_data_type, int image_width, int image_height, int fov_axis, float zoom,
+                         const float screen_center[2], void* stream) {
+  if (!exposure || !background_color || !image || !screen_center) return rb_fail(NRF_E_INVALID, "null argument");
+  if (output_color_space < 0 || output_color_space > 2) return rb_fail(NRF_E_INVALID, "bad color space");
+  if (image_data_type != NRF_IMG_BYTE && image_data_type != NRF_IMG_HALF && image_data_type != NRF_IMG_FLOAT)
+    return rb_fail(NRF_E_INVALID, "bad image data type");
+  if (!overlay_size_valid(image_width) || !overlay_size_valid(image_height)) return rb_fail(NRF_E_INVALID, "bad image resolution (1 .. 16384 per axis)");
+  if (fov_axis != 0 && fov_axis != 1) return rb_fail(NRF_E_INVALID, "bad fov axis");
+  if (!std::isfinite(zoom) || zoom == 0.0f) return rb_fail(NRF_E_INVALID, "bad zoom (finite and not zero)");
+  if (!std::isfinite(screen_center[0]) || !std::isfinite(screen_center[1])) return rb_fail(NRF_E_INVALID, "bad screen center (finite)");
+  RB_READY();
+  (void)n;
+  if (!overlay_size_valid(rb->W) || !overlay_size_valid(rb->H)) return rb_fail(NRF_E_INVALID, "the surface is larger than 16384 on an axis");
+  if (image_data_type == NRF_IMG_BYTE && !rb->srgb8) {  // the table, once per buffer
+    void* t = nullptr;
+    RB_TRY(hipMalloc(&t, 256 * sizeof(float)));
+    const hipError_t e = hipMemcpy(t, srgb8_table(), 256 * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(t);
+      return rb_hip(e, "uploading the sRGB table");
+    }
+    rb->srgb8 = t;
+  }
+  nrf::OverlayImage A{};
+  A.map = {rb->W, rb->H, image_width, image_height, fov_axis, zoom, screen_center[0], screen_center[1]};
+  A.alpha = alpha;
+  for (int k = 0; k < 3; ++k) A.gain[k] = powf(2.0f, exposure[k]);
+  const float given[4] = {background_color[0], background_color[1], background_color[2], background_color[3]};
+  nrf::overlay_background(given, rb->color_space, A.bg);
+  A.render_space = rb->color_space;
+  A.display_space = output_color_space;
+  A.film = film_curve(rb->curve);
+  RB_TRY((hipError_t)nrf::launch_overlay_image(A, image, image_data_type, (const float*)rb->srgb8, rb->surface, st));
+  if (!stream) RB_TRY(hipStreamSynchronize(st));
+  return NRF_OK;
+}
+
+int nrf_rb_overlay_false_color(nrf_render_buffer* rb, int training_width, int training_height, int fov_axis, const void* error_map,
+                               int map_width, int map_height, const void* average, float brightness, int viridis, void* stream) {
+  if (!error_map || !average) return rb_fail(NRF_E_INVALID, "null argument");
+  if (!overlay_size_valid(training_width) || !overlay_size_valid(training_height))
+    return rb_fail(NRF_E_INVALID, "bad training resolution (1 .. 16384 per axis)");
+  if (fov_axis != 0 && fov_axis != 1) return rb_fail(NRF_E_INVALID, "bad fov axis");
+  if (map_width < 1 || map_width > nrf::ERROR_MAP_MAX || map_height < 1 || map_height > nrf::ERROR_MAP_MAX)
+    return rb_fail(NRF_E_INVALID, "bad error map resolution (1 .. 512 per axis)");
+  RB_READY();
+  (void)n;
+  if (!overlay_size_valid(rb->W) || !overlay_size_valid(rb->H)) return rb_fail(NRF_E_INVALID, "the surface is larger than 16384 on an axis");
+  const nrf::OverlayFalseColor A{rb->W, rb->H, training_width, training_height, map_width, map_height, fov_axis, brightness, viridis ? 1 : 0};
+  RB_TRY((hipError_t)nrf::launch_overlay_false_color(A, (const float*)error_map, (const float*)average, rb->surface, st));
+  if (!stream) RB_TRY(hipStreamSynchronize(st));
+  return NRF_OK;
+}
+
+int nrf_rb_error_map(nrf_render_buffer* rb, const void* truth_f32x4, int map_width, int map_height, void* error_map, void* average,
+                     void* stream) {
+  if (!truth_f32x4 || !error_map || !average) return rb_fail(NRF_E_INVALID, "null argument");
+  RB_READY();
+  (void)n;
+  if (!overlay_size_valid(rb->W) || !overlay_size_valid(rb->H)) return rb_fail(NRF_E_INVALID, "the surface is larger than 16384 on an axis");
+  if (!nrf::error_map_axis_valid(rb->W, map_width) || !nrf::error_map_axis_valid(rb->H, map_height))
+    return rb_fail(NRF_E_INVALID, "bad error map resolution (1 <= cells <= min(pixels, 512) per axis)");
+  RB_TRY((hipError_t)nrf::launch_error_map(rb->W, rb->H, map_width, map_height, rb->surface, truth_f32x4, (float*)error_map, (float*)average, st));
   if (!stream) RB_TRY(hipStreamSynchronize(st));
   return NRF_OK;
 }

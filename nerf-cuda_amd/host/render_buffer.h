@@ -1,10 +1,11 @@
 // render_buffer.h -- C++ mirror of the reference's ngp::CudaRenderBuffer presentation API
 // (include/nerf-cuda/render_buffer.h:160-315) on the C ABI: same method names for resize,
 // reset_accumulation, spp, frame/depth/accumulate buffers, clear_frame, accumulate, tonemap,
-// host_to_accumulate_buffer, accumulate_buffer_host, overlay_depth; enable_upscale / set_upscale_sharpening / upscale stand where the
+// host_to_accumulate_buffer, accumulate_buffer_host, overlay_depth, overlay_image, overlay_false_color (error_map makes what the last one
+// reads: the reference fills its error map while training); enable_upscale / set_upscale_sharpening / upscale stand where the
 // reference has DLSS (a proprietary binary: the deterministic spatial upscaler of nrf_rb_upscale instead, and upscale_temporal, the
-// accumulator over jittered frames of nrf_rb_upscale_temporal).  GL textures, CUDA surfaces and
-// the image / false-colour overlays of the reference class are out of scope (NVIDIA/GL presentation, training views).
+// accumulator over jittered frames of nrf_rb_upscale_temporal).  GL textures and CUDA surfaces of the reference class are out of scope
+// (NVIDIA/GL presentation): the surface is a plain float4 plane.
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -16,6 +17,7 @@
 namespace ngp {
 
 enum class EColorSpace : int { Linear = NRF_CS_LINEAR, SRGB = NRF_CS_SRGB, VisPosNeg = NRF_CS_VISPOSNEG };
+enum class EImageDataType : int { None = 0, Byte = NRF_IMG_BYTE, Half = NRF_IMG_HALF, Float = NRF_IMG_FLOAT };
 enum class ETonemapCurve : int { Identity = NRF_TM_IDENTITY, ACES = NRF_TM_ACES, Hable = NRF_TM_HABLE, Reinhard = NRF_TM_REINHARD };
 
 class RenderBuffer {
@@ -97,6 +99,29 @@ class RenderBuffer {
   void overlay_depth(float alpha, const float* depth, float depth_scale, const Vector2i& resolution, int fov_axis, float zoom,
                      const float screen_center[2], void* stream = nullptr) {
     ok(nrf_rb_overlay_depth(m_rb, alpha, depth, depth_scale, resolution[0], resolution[1], fov_axis, zoom, screen_center, stream));
+  }
+  // overlay_image(), render_buffer.h:244-257: `image` is a device image of `image_resolution` texels of `image_data_type` (Byte: uint32
+  // sRGB texels with straight alpha; Half / Float: four premultiplied linear values), put over `background_color`, developed with the
+  // per-channel `exposure` and the buffer's curve, and blended over the surface with weight `alpha` (nrf_rb_overlay_image)
+  void overlay_image(float alpha, const float exposure[3], const float background_color[4], EColorSpace output_color_space, const void* image,
+                     EImageDataType image_data_type, const Vector2i& image_resolution, int fov_axis, float zoom, const float screen_center[2],
+                     void* stream = nullptr) {
+    ok(nrf_rb_overlay_image(m_rb, alpha, exposure, background_color, (int)output_color_space, image, (int)image_data_type, image_resolution[0],
+                            image_resolution[1], fov_axis, zoom, screen_center, stream));
+  }
+  // overlay_false_color(), render_buffer.h:270: the surface's grey times the colour map of a device error map over its average.
+  // `to_srgb` is accepted and ignored: it is dead in the reference's kernel (nrf_rb_overlay_false_color)
+  void overlay_false_color(const Vector2i& training_resolution, bool to_srgb, int fov_axis, void* stream, const float* error_map,
+                           const Vector2i& error_map_resolution, const float* average, float brightness, bool viridis) {
+    (void)to_srgb;
+    ok(nrf_rb_overlay_false_color(m_rb, training_resolution[0], training_resolution[1], fov_axis, error_map, error_map_resolution[0],
+                                  error_map_resolution[1], average, brightness, viridis ? 1 : 0, stream));
+  }
+  // what overlay_false_color reads, made on the device: the per-cell mean squared error of the surface against a device float4 plane of
+  // the surface's size, and the mean of the cells (nrf_rb_error_map); error_map: device float [h][w] of error_map_resolution,
+  // average: one device float
+  void error_map(const void* truth, const Vector2i& error_map_resolution, float* error_map, float* average, void* stream = nullptr) {
+    ok(nrf_rb_error_map(m_rb, truth, error_map_resolution[0], error_map_resolution[1], error_map, average, stream));
   }
 
  private:

@@ -26,6 +26,13 @@
 //   reference drives DLSS: frame k is rendered with the sub-pixel jitter of RenderBuffer::upscale_jitter(k) (frame 0 without, as a
 //   reset), developed alone into the surface, and accumulated at the output resolution (RenderBuffer::upscale_temporal); upscaled.png
 //   is the presented plane after the last frame
+//   [--overlay_image FILE.ppm [--overlay_alpha A]] -- an 8-bit binary PPM (P6, maxval 255) of the frame's size is uploaded as Byte texels
+//   with alpha 255 and blended with weight A (default 0.5) over the developed frame on the device before tonemapped.png is written
+//   (RenderBuffer::overlay_image: the photograph next to the render)
+//   [--compare FILE.ppm] -- the same kind of file is uploaded as a float4 truth plane (v / 255, alpha 1); the per-cell mean squared error
+//   of the developed frame against it is reduced on the device at min(128, W) x min(128, H) cells (RenderBuffer::error_map), the average
+//   and -10 log10(average) are printed, and the frame under the viridis false colours of that map is written as error.png
+//   (RenderBuffer::overlay_false_color)
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -36,6 +43,7 @@
 #include <iostream>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "nerf_render.h"
 #include "png_lite.h"
@@ -98,6 +106,72 @@ class DeviceTimer {
   void *m_stream = nullptr, *m_begin = nullptr, *m_end = nullptr;
 };
 
+// Device memory of the HIP runtime that libnerfhip.so has loaded, looked up by name like the timer's calls
+class DeviceBuffer {
+ public:
+  explicit DeviceBuffer(size_t bytes) : m_bytes(bytes) {
+    malloc_ = sym<int (*)(void**, size_t)>("hipMalloc");
+    free_ = sym<int (*)(void*)>("hipFree");
+    memcpy_ = sym<int (*)(void*, const void*, size_t, int)>("hipMemcpy");
+    ok(malloc_(&m_ptr, bytes));
+  }
+  ~DeviceBuffer() {
+    if (m_ptr) free_(m_ptr);
+  }
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  void* ptr() const { return m_ptr; }
+  void upload(const void* host) { ok(memcpy_(m_ptr, host, m_bytes, 1)); }    // hipMemcpyHostToDevice
+  void download(void* host) const { ok(memcpy_(host, m_ptr, m_bytes, 2)); }  // hipMemcpyDeviceToHost
+
+ private:
+  template <class F>
+  static F sym(const char* name) {
+    void* p = dlsym(RTLD_DEFAULT, name);
+    if (!p) throw std::runtime_error{std::string("the HIP runtime has no ") + name};
+    return reinterpret_cast<F>(p);
+  }
+  static void ok(int rc) {
+    if (rc != 0) throw std::runtime_error{"HIP runtime error " + std::to_string(rc) + " on a device buffer"};
+  }
+  int (*malloc_)(void**, size_t) = nullptr;
+  int (*free_)(void*) = nullptr;
+  int (*memcpy_)(void*, const void*, size_t, int) = nullptr;
+  void* m_ptr = nullptr;
+  size_t m_bytes = 0;
+};
+
+// An 8-bit binary PPM (P6) of exactly W x H pixels: the rgb bytes.  Refused: another magic, a size that is not the frame's, a maxval
+// other than 255, a file that ends before the last pixel
+static std::vector<unsigned char> read_ppm(const std::string& path, int W, int H) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) throw std::runtime_error{"cannot open " + path};
+  char magic[3] = {0, 0, 0};
+  int w = 0, h = 0, maxval = 0;
+  const bool header = std::fscanf(f, "%2s %d %d %d", magic, &w, &h, &maxval) == 4 && std::string(magic) == "P6" && std::fgetc(f) != EOF;
+  std::vector<unsigned char> rgb;
+  if (header && w == W && h == H && maxval == 255) {
+    rgb.resize((size_t)W * H * 3);
+    if (std::fread(rgb.data(), 1, rgb.size(), f) != rgb.size()) rgb.clear();
+  }
+  std::fclose(f);
+  if (!header) throw std::runtime_error{path + " is not a binary PPM (P6)"};
+  if (w != W || h != H) throw std::runtime_error{path + " is " + std::to_string(w) + " x " + std::to_string(h) + ", the frame is " + std::to_string(W) + " x " + std::to_string(H)};
+  if (maxval != 255) throw std::runtime_error{path + " has maxval " + std::to_string(maxval) + ", not 255"};
+  if (rgb.empty()) throw std::runtime_error{path + " ends before its last pixel"};
+  return rgb;
+}
+
+static void write_surface_png(const std::string& path, int W, int H, const std::vector<float>& rgba) {
+  std::vector<unsigned char> out((size_t)W * H * 3);
+  for (size_t i = 0; i < (size_t)W * H; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const float v = rgba[i * 4 + j] * 255;
+      out[i * 3 + j] = (unsigned char)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
+    }
+  pnglite::write(path.c_str(), W, H, 3, out.data());
+}
+
 int main(int argc, char** argv) {
   std::cout << "Hello, Metavese!" << std::endl;
   // the options, taken out of argv: what remains are the positional arguments above
@@ -111,15 +185,20 @@ int main(int argc, char** argv) {
   int mesh_texture = 0, mesh_texture_width = 4096;  // (off)
   float upscale = 0.0f, upscale_sharpening = 0.0f;  // (off)
   int upscale_temporal = 0;                          // (off)
+  std::string overlay_path, compare_path;            // (off)
+  float overlay_alpha = 0.5f;
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       const std::string a = argv[i];
       if ((a == "--save_mesh" || a == "--mesh_res" || a == "--mesh_iso" || a == "--mesh_min_triangles" || a == "--mesh_refine" ||
            a == "--mesh_simplify" || a == "--mesh_texture" || a == "--mesh_texture_width" || a == "--upscale" || a == "--upscale_sharpening" ||
-           a == "--upscale_temporal") &&
+           a == "--upscale_temporal" || a == "--overlay_image" || a == "--overlay_alpha" || a == "--compare") &&
           i + 1 < argc) {
         if (a == "--save_mesh") mesh_path = argv[++i];
+        else if (a == "--overlay_image") overlay_path = argv[++i];
+        else if (a == "--overlay_alpha") overlay_alpha = (float)std::atof(argv[++i]);
+        else if (a == "--compare") compare_path = argv[++i];
         else if (a == "--upscale") upscale = (float)std::atof(argv[++i]);
         else if (a == "--upscale_sharpening") upscale_sharpening = (float)std::atof(argv[++i]);
         else if (a == "--upscale_temporal") upscale_temporal = std::atoi(argv[++i]);
@@ -139,11 +218,15 @@ int main(int argc, char** argv) {
     argc = kept;
   }
   try {
+    const int W = argc > 3 ? std::atoi(argv[2]) : 4000 / 8, H = argc > 3 ? std::atoi(argv[3]) : 4000 / 8;
+    const std::string prefix = argc > 4 ? argv[4] : "./";
+    // the pictures of --overlay_image and --compare, read before anything is loaded or rendered: a file that does not fit ends the run here
+    std::vector<unsigned char> overlay_rgb, compare_rgb;
+    if (!overlay_path.empty()) overlay_rgb = read_ppm(overlay_path, W, H);
+    if (!compare_path.empty()) compare_rgb = read_ppm(compare_path, W, H);
     NerfRender* render = new NerfRender();
     const std::string config_path = argc > 1 ? argv[1] : "freality.msgpack";
     render->reload_network_from_file(config_path);  // Init Model
-    const int W = argc > 3 ? std::atoi(argv[2]) : 4000 / 8, H = argc > 3 ? std::atoi(argv[3]) : 4000 / 8;
-    const std::string prefix = argc > 4 ? argv[4] : "./";
     const float s = (float)W / 500.0f;
     Camera cam = {3550.115f / 8 * s, 3554.515f / 8 * s, 3010.45f / 8 * s, 1996.027f / 8 * s};
     Matrix4f pos;
@@ -169,14 +252,19 @@ int main(int argc, char** argv) {
       rb.host_to_accumulate_buffer(img.rgb, img.W * img.H);
       const float bg[4] = {0.f, 0.f, 0.f, 1.f};
       rb.tonemap(0.0f, bg, EColorSpace::SRGB);
-      const std::vector<float> result = rb.surface_host();
-      std::vector<unsigned char> out((size_t)img.W * img.H * 3);
-      for (size_t i = 0; i < (size_t)img.W * img.H; ++i)
-        for (int j = 0; j < 3; ++j) {
-          const float v = result[i * 4 + j] * 255;
-          out[i * 3 + j] = (unsigned char)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
-        }
-      pnglite::write((prefix + "tonemapped.png").c_str(), img.W, img.H, 3, out.data());
+      if (!overlay_path.empty()) {
+        // the photograph over the developed frame, on the device: Byte texels (sRGB, alpha 255) through the same tonemap as the frame
+        const std::vector<unsigned char>& rgb = overlay_rgb;
+        std::vector<uint32_t> texels((size_t)img.W * img.H);
+        for (size_t i = 0; i < texels.size(); ++i)
+          texels[i] = (uint32_t)rgb[i * 3] | (uint32_t)rgb[i * 3 + 1] << 8 | (uint32_t)rgb[i * 3 + 2] << 16 | 0xFF000000u;
+        DeviceBuffer image(texels.size() * sizeof(uint32_t));
+        image.upload(texels.data());
+        const float exposure[3] = {0.f, 0.f, 0.f}, center[2] = {0.5f, 0.5f};
+        rb.overlay_image(overlay_alpha, exposure, bg, EColorSpace::SRGB, image.ptr(), EImageDataType::Byte, Vector2i(img.W, img.H), 0, 1.0f, center);
+        std::printf("overlay: %s over the frame, alpha %g\n", overlay_path.c_str(), overlay_alpha);
+      }
+      write_surface_png(prefix + "tonemapped.png", img.W, img.H, rb.surface_host());
       if (upscale != 0.0f) {
         // main.cu:171-206 hands the frame to DLSS at out_resolution = 2 x in_resolution and writes dlss.png; here the surface just
         // developed goes through the upscaler on the device, on a stream of this program's so that a pair of events times the launch
@@ -218,6 +306,25 @@ int main(int argc, char** argv) {
             up8[i * 3 + j] = (unsigned char)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));
           }
         pnglite::write((prefix + "upscaled.png").c_str(), got[0], got[1], 3, up8.data());
+      }
+      if (!compare_path.empty()) {
+        // where the developed frame is wrong: the file as the truth plane, the error map and its average on the device, then the frame
+        // under the map's false colours (last: it changes the surface)
+        const std::vector<unsigned char>& rgb = compare_rgb;
+        std::vector<float> truth((size_t)img.W * img.H * 4);
+        for (size_t i = 0; i < (size_t)img.W * img.H; ++i) {
+          for (int j = 0; j < 3; ++j) truth[i * 4 + j] = (float)rgb[i * 3 + j] / 255.0f;
+          truth[i * 4 + 3] = 1.0f;
+        }
+        const Vector2i cells(std::min(128, img.W), std::min(128, img.H));
+        DeviceBuffer plane(truth.size() * sizeof(float)), map((size_t)cells[0] * cells[1] * sizeof(float)), average(sizeof(float));
+        plane.upload(truth.data());
+        rb.error_map(plane.ptr(), cells, (float*)map.ptr(), (float*)average.ptr());
+        float mse = 0.f;
+        average.download(&mse);
+        std::printf("compare: %d x %d cells, average %.9g, %.4f dB\n", cells[0], cells[1], mse, -10.0 * std::log10((double)mse));
+        rb.overlay_false_color(Vector2i(img.W, img.H), false, 0, nullptr, (const float*)map.ptr(), cells, (const float*)average.ptr(), 1.0f, true);
+        write_surface_png(prefix + "error.png", img.W, img.H, rb.surface_host());
       }
     }
     FILE* f = std::fopen((prefix + "image.rgb").c_str(), "wb");  // raw copy for the parity test

@@ -380,6 +380,12 @@ _SIGS = {
                                        C.POINTER(C.c_float), C.c_void_p]),
     "nrf_rb_host_to_accumulate_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "nrf_rb_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_rb_srgb8_table": (C.c_int, [C.POINTER(C.c_float)]),
+    "nrf_rb_overlay_image": (C.c_int, [C.c_void_p, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p]),
+    "nrf_rb_overlay_false_color": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float,
+                                             C.c_int, C.c_void_p]),
+    "nrf_rb_error_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_rb_enable_upscale": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "nrf_rb_disable_upscale": (C.c_int, [C.c_void_p]),
     "nrf_rb_set_upscale_sharpening": (C.c_int, [C.c_void_p, C.c_float]),
@@ -473,6 +479,13 @@ def default_per_level_scale(bound: float, base_resolution: int, n_levels: int) -
     out = C.c_float()
     _check(load_library().nrf_default_per_level_scale(C.c_float(bound), base_resolution, n_levels, C.byref(out)))
     return float(out.value)
+
+
+def srgb8_table():
+    """float32 [256]: srgb_to_linear(b / 255) as the image overlay reads a Byte texel's channels (nrf_rb_srgb8_table; host only)."""
+    t = (C.c_float * 256)()
+    _check(load_library().nrf_rb_srgb8_table(t))
+    return np.frombuffer(t, np.float32).copy()
 
 
 def upscale_jitter(k: int):
@@ -1165,6 +1178,7 @@ def normals_from_gradients(out):
 
 CS_LINEAR, CS_SRGB, CS_VISPOSNEG = 0, 1, 2
 TM_IDENTITY, TM_ACES, TM_HABLE, TM_REINHARD = 0, 1, 2, 3
+IMG_BYTE, IMG_HALF, IMG_FLOAT = 1, 2, 3  # EImageDataType: uint32 sRGB texels with straight alpha, four fp16, four fp32
 
 
 class NerfGroup:
@@ -1397,6 +1411,30 @@ class RenderBuffer:
         ctr = np.ascontiguousarray(screen_center, np.float32).reshape(2)
         _check(self.lib.nrf_rb_overlay_depth(self.h, C.c_float(alpha), C.c_void_p(depth_ptr), C.c_float(depth_scale), image_width,
                                              image_height, fov_axis, C.c_float(zoom), _fptr(ctr), C.c_void_p(stream or 0)))
+
+    def overlay_image(self, alpha, exposure, background_color, output_color_space, image_ptr, image_data_type, image_width, image_height,
+                      fov_axis=0, zoom=1.0, screen_center=(0.5, 0.5), stream=None):
+        """a device image of IMG_BYTE / IMG_HALF / IMG_FLOAT texels over its background, developed and blended over the surface with
+        weight alpha (nrf_rb_overlay_image); exposure: one value or one per channel"""
+        e = np.ascontiguousarray(np.broadcast_to(np.asarray(exposure, np.float32), (3,)))
+        bg = np.ascontiguousarray(background_color, np.float32).reshape(4)
+        ctr = np.ascontiguousarray(screen_center, np.float32).reshape(2)
+        _check(self.lib.nrf_rb_overlay_image(self.h, C.c_float(alpha), _fptr(e), _fptr(bg), output_color_space, C.c_void_p(image_ptr or 0),
+                                             image_data_type, image_width, image_height, fov_axis, C.c_float(zoom), _fptr(ctr),
+                                             C.c_void_p(stream or 0)))
+
+    def overlay_false_color(self, training_width, training_height, fov_axis, error_map_ptr, map_width, map_height, average_ptr,
+                            brightness=1.0, viridis=True, stream=None):
+        """the surface's grey times the colour map of a device error map over its average (nrf_rb_overlay_false_color)"""
+        _check(self.lib.nrf_rb_overlay_false_color(self.h, training_width, training_height, fov_axis, C.c_void_p(error_map_ptr or 0),
+                                                   map_width, map_height, C.c_void_p(average_ptr or 0), C.c_float(brightness),
+                                                   int(bool(viridis)), C.c_void_p(stream or 0)))
+
+    def error_map(self, truth_ptr, map_width, map_height, error_map_ptr, average_ptr, stream=None):
+        """the per-cell mean squared error of the surface against a device float4 truth plane, and the mean of the cells
+        (nrf_rb_error_map); error_map_ptr: device float [map_height][map_width], average_ptr: one device float"""
+        _check(self.lib.nrf_rb_error_map(self.h, C.c_void_p(truth_ptr or 0), map_width, map_height, C.c_void_p(error_map_ptr or 0),
+                                         C.c_void_p(average_ptr or 0), C.c_void_p(stream or 0)))
 
     def host_to_accumulate_buffer(self, rgb_u8):
         rgb = np.ascontiguousarray(rgb_u8, np.uint8)
