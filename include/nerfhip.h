@@ -514,7 +514,12 @@ int nrf_encode_dir(nrf_context* ctx, const void* dir01, uint32_t n, void* out_f1
 /* kernel_mlp_fused x2 + extract_density (nerf_network.h:148-196) on
  * pre-encoded inputs: feat fp16 [n][feature width], dirfeat fp16 [n][dir
  * width] (the widths of nrf_encode_grid / nrf_encode_dir: 32 and 16 for the
- * base configuration) -> out fp16 [n][4] = (r,g,b,sigma)                     */
+ * base configuration) -> out fp16 [n][4] = (r,g,b,sigma).
+ * Alignment: feat_f16 16 bytes, dirfeat_f16 and out_f16 8 bytes (the base
+ * configuration's kernel reads a row in 16- and 8-byte pieces and writes a
+ * row in one 8-byte store; models that go through the generic stage need
+ * 2 bytes for the two inputs and 8 for out_f16).  Anything else is refused
+ * with NRF_E_INVALID before a kernel is launched.                            */
 int nrf_mlp_forward(nrf_context* ctx, const void* feat_f16, const void* dirfeat_f16,
                     uint32_t n, void* out_f16, void* stream);
 /* Measurement aid: the same call, every chunk of samples evaluated `repeat`

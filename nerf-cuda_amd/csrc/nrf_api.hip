@@ -1862,7 +1862,13 @@ int nrf_mlp_forward_repeat(nrf_context* c, const void* feat, const void* dirfeat
   STAGE_PROLOGUE();
   if (n && (!feat || !dirfeat || !out)) return fail(NRF_E_INVALID, "null argument");
   if (repeat < 1) return fail(NRF_E_INVALID, "repeat must be >= 1");
-  HIP_TRY(launch_mlp_forward(stage_model(c), feat, dirfeat, n, out, repeat, st));
+  const DevModel m = stage_model(c);
+  // the hot stage reads a lane's 16 bytes of its feature row and 8 of its direction row in one load each and writes a row's four
+  // halves in one 8-byte store; the generic stage reads halves and writes the same 8-byte rows
+  const uintptr_t in_mask = m.stage == NET_GENERIC ? 1u : 15u, dir_mask = m.stage == NET_GENERIC ? 1u : 7u;
+  if (n && (((uintptr_t)feat & in_mask) || ((uintptr_t)dirfeat & dir_mask) || ((uintptr_t)out & 7u)))
+    return fail(NRF_E_INVALID, "feat must be 16-byte aligned, dirfeat and out 8-byte aligned (generic stage: feat and dirfeat 2-byte aligned)");
+  HIP_TRY(launch_mlp_forward(m, feat, dirfeat, n, out, repeat, st));
   STAGE_EPILOGUE();
 }
 

@@ -8,6 +8,7 @@
 
 #include "nrf_frame_plan.h"
 #include "nrf_render.h"
+#include "nrf_stage_plan.h"
 
 namespace nrf {
 
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void gen_encode_grid_kernel(const DevModel M, 
 
 __global__ __launch_bounds__(256) void encode_dir_kernel(const DevModel M, const float* __restrict__ dir01, uint32_t n,
                                                          uint32_t* __restrict__ out) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     half_t e[16];
     encode_dir16(M, dir01[3 * (size_t)i], dir01[3 * (size_t)i + 1], dir01[3 * (size_t)i + 2], e);
 #pragma unroll
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(256) void encode_dir_kernel(const DevModel M, const
 __global__ __launch_bounds__(256) void gen_encode_dir_kernel(const DevModel M, const float* __restrict__ dir01, uint32_t n,
                                                              half_t* __restrict__ out) {
   const GenModel& G = *M.gen;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
     gen_encode_dir(M, G, dir01[3 * (size_t)i], dir01[3 * (size_t)i + 1], dir01[3 * (size_t)i + 2], out + (size_t)i * G.dir_w);
 }
 
@@ -390,9 +391,9 @@ __global__ __launch_bounds__(256, 2) void network_kernel(const DevModel M, const
 __global__ __launch_bounds__(256) void generate_rays_kernel(const DevModel M, const FrameParams P, float* __restrict__ rays_o,
                                                             float* __restrict__ rays_d, float* __restrict__ nears,
                                                             float* __restrict__ fars) {
-  const int n = P.W * P.H;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int px = i % P.W, py = i / P.W;
+  const int64_t n = (int64_t)P.W * P.H;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int px = (int)(i % P.W), py = (int)(i / P.W);
     const float o[3] = {P.org[0], P.org[1], P.org[2]};
     float d[3], nr, fr;
     ray_dir(P.R, P.cam, px, py, d);
@@ -411,14 +412,14 @@ __global__ __launch_bounds__(256) void march_kernel(const DevModel M, float dt_g
                                                     float* __restrict__ xyzs, float* __restrict__ dirs,
                                                     float* __restrict__ deltas, uint32_t perturb) {
   const MarchConst mc = march_const(M, dt_gamma);
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     const float ox = rays_o[3 * (size_t)i], oy = rays_o[3 * (size_t)i + 1], oz = rays_o[3 * (size_t)i + 2];
     const float dx = rays_d[3 * (size_t)i], dy = rays_d[3 * (size_t)i + 1], dz = rays_d[3 * (size_t)i + 2];
     const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
     const int sx = __builtin_signbitf(dx) ? 0 : 1, sy = __builtin_signbitf(dy) ? 0 : 1, sz = __builtin_signbitf(dz) ? 0 : 1;
     const float far = fars[i];
     float t = rays_t[i];  // kernel_march_rays with an explicit n_step: render_utils.h:591-653
-    if (perturb) t = t + mc.dt_min * pcg32_first_float((uint64_t)i, (uint64_t)perturb);  // :585-589, n = the ray's place in the call
+    if (perturb) t = t + mc.dt_min * pcg32_first_float(i, (uint64_t)perturb);  // :585-589, n = the ray's place in the call
     float last_t = t;
     bool marching = true;
     for (uint32_t k = 0; k < n_step; ++k) {
@@ -449,7 +450,7 @@ __global__ __launch_bounds__(256) void march_kernel(const DevModel M, float dt_g
 __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                         const float* __restrict__ deltas, uint32_t n, uint32_t n_step,
                                                         float* __restrict__ rays_t, float* __restrict__ state) {
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     float* st = state + 5 * (size_t)i;
     float ws = st[0], dep = st[1], cr = st[2], cg = st[3], cb = st[4];
     float t = rays_t[i];
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(256) void untile_kernel(const float* __restrict__ g
 
 __global__ __launch_bounds__(256) void quantize_kernel(const float4* __restrict__ rgba, const float* __restrict__ depth, int n,
                                                        unsigned char* __restrict__ rgb8, unsigned char* __restrict__ depth8) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float4 v = rgba[i];
     rgb8[3 * (size_t)i] = quant_u8(v.x);
     rgb8[3 * (size_t)i + 1] = quant_u8(v.y);
@@ -749,6 +750,9 @@ __global__ __launch_bounds__(PLAN_SORT_THREADS) void plan_sort_kernel(const View
 }
 
 // ---------------------------------------------------------------- launchers ----
+// The stage kernels and the pixel-format kernels take their grids from nrf_stage_plan.h (stage_workgroups): block size, items per
+// workgroup and cap of every kind are stated there, for the tests that mean to walk a loop more than once.
+static inline int stage_grid(int kernel, uint64_t n, int arg = 0) { return stage_workgroups(StageKind{kernel, arg}, n); }
 static inline int grid_for(uint64_t n, int block = 256, int cap = 256 * 8) {
   uint64_t g = (n + block - 1) / block;
   if (g < 1) g = 1;
@@ -864,13 +868,13 @@ hipError_t launch_build_quads(const void* table, uint32_t res, uint32_t size, bo
 hipError_t launch_encode_grid(const DevModel& M, const void* pos01, uint32_t n, void* out, hipStream_t st, bool fast_interp) {
   if (!n) return hipSuccess;
   if (M.stage == NET_GENERIC)
-    hipLaunchKernelGGL(gen_encode_grid_kernel, dim3(grid_for((uint64_t)n * M.n_levels)), dim3(256), 0, st, M, (const float*)pos01, n,
+    hipLaunchKernelGGL(gen_encode_grid_kernel, dim3(stage_grid(STAGE_GEN_ENCODE_GRID, n, (int)M.n_levels)), dim3(256), 0, st, M, (const float*)pos01, n,
                        (half_t*)out);
   else if (fast_interp)
-    hipLaunchKernelGGL(encode_grid_kernel<true>, dim3(grid_for((uint64_t)n * 16)), dim3(256), 0, st, M, (const float*)pos01, n,
+    hipLaunchKernelGGL(encode_grid_kernel<true>, dim3(stage_grid(STAGE_ENCODE_GRID, n)), dim3(256), 0, st, M, (const float*)pos01, n,
                        (uint32_t*)out);
   else
-    hipLaunchKernelGGL(encode_grid_kernel<false>, dim3(grid_for((uint64_t)n * 16)), dim3(256), 0, st, M, (const float*)pos01, n,
+    hipLaunchKernelGGL(encode_grid_kernel<false>, dim3(stage_grid(STAGE_ENCODE_GRID, n)), dim3(256), 0, st, M, (const float*)pos01, n,
                        (uint32_t*)out);
   return hipGetLastError();
 }
@@ -878,9 +882,9 @@ hipError_t launch_encode_grid(const DevModel& M, const void* pos01, uint32_t n, 
 hipError_t launch_encode_dir(const DevModel& M, const void* dir01, uint32_t n, void* out, hipStream_t st) {
   if (!n) return hipSuccess;
   if (M.stage == NET_GENERIC)
-    hipLaunchKernelGGL(gen_encode_dir_kernel, dim3(grid_for(n)), dim3(256), 0, st, M, (const float*)dir01, n, (half_t*)out);
+    hipLaunchKernelGGL(gen_encode_dir_kernel, dim3(stage_grid(STAGE_GEN_ENCODE_DIR, n)), dim3(256), 0, st, M, (const float*)dir01, n, (half_t*)out);
   else
-    hipLaunchKernelGGL(encode_dir_kernel, dim3(grid_for(n)), dim3(256), 0, st, M, (const float*)dir01, n, (uint32_t*)out);
+    hipLaunchKernelGGL(encode_dir_kernel, dim3(stage_grid(STAGE_ENCODE_DIR, n)), dim3(256), 0, st, M, (const float*)dir01, n, (uint32_t*)out);
   return hipGetLastError();
 }
 
@@ -891,13 +895,13 @@ hipError_t launch_mlp_forward(const DevModel& M, const void* feat, const void* d
     const int lds = gen_lds_bytes(M, 4);
     hipError_t e = allow_lds(gen_mlp_forward_kernel, lds);
     if (e != hipSuccess) return e;
-    const uint64_t chunks = ((uint64_t)n + GEN_SAMPLES - 1) / GEN_SAMPLES;
+    static_assert(GEN_SAMPLES == STAGE_GEN_MLP_ROWS, "nrf_stage_plan.h states the rows of a wave's chunk");
     for (uint32_t r = 0; r < (repeat ? repeat : 1u); ++r)  // (the repeat count is a measurement aid of the hot instance)
-      hipLaunchKernelGGL(gen_mlp_forward_kernel, dim3(grid_for(chunks, 4, 256 * 4)), dim3(256), lds, st, M, (const half_t*)feat,
+      hipLaunchKernelGGL(gen_mlp_forward_kernel, dim3(stage_grid(STAGE_GEN_MLP_FORWARD, n)), dim3(256), lds, st, M, (const half_t*)feat,
                          (const half_t*)dirfeat, n, (uint2*)out);
     return hipGetLastError();
   }
-  const uint64_t chunks = ((uint64_t)n + 16 * MLP_TILES - 1) / (16 * MLP_TILES);
+  static_assert(16 * MLP_TILES == STAGE_MLP_ROWS, "nrf_stage_plan.h states the rows of a wave's chunk");
   // the kernel's form: workgroups per CU its registers are budgeted for x how the prefetch buffers rotate (mlp_forward_kernel).
   // NRF_MLP_FORM = 30 (3 per CU, copies: rounds 1-4) | 20 | 21 (2 per CU, by name) -- A/B runs; default: MLP_FORM_DEFAULT.
   // (3 per CU by name needs 176 registers: built, it spilled 8-11 of them -- not shipped)
@@ -906,14 +910,14 @@ hipError_t launch_mlp_forward(const DevModel& M, const void* feat, const void* d
     const int f = e ? std::atoi(e) : MLP_FORM_DEFAULT;
     return (f == 30 || f == 20 || f == 21) ? f : MLP_FORM_DEFAULT;
   }();
-#define NRF_LAUNCH_MLP(R, OCC, NAMED)                                                                                     \
-  hipLaunchKernelGGL((mlp_forward_kernel<R, OCC, NAMED>), dim3(grid_for(chunks, 4, 256 * OCC)), dim3(256), 0, st, M,      \
-                     (const uint4*)feat, (const uint2*)dirfeat, n, (half_t*)out, repeat)
+#define NRF_LAUNCH_MLP(R, FORM, NAMED)                                                                                    \
+  hipLaunchKernelGGL((mlp_forward_kernel<R, stage_mlp_occ(FORM), NAMED>), dim3(stage_grid(STAGE_MLP_FORWARD, n, FORM)),   \
+                     dim3(256), 0, st, M, (const uint4*)feat, (const uint2*)dirfeat, n, (half_t*)out, repeat)
 #define NRF_LAUNCH_MLP_FORM(R)                                                                                            \
   do {                                                                                                                    \
-    if (form == 20) NRF_LAUNCH_MLP(R, 2, false);                                                                          \
-    else if (form == 21) NRF_LAUNCH_MLP(R, 2, true);                                                                      \
-    else NRF_LAUNCH_MLP(R, 3, false);                                                                                     \
+    if (form == 20) NRF_LAUNCH_MLP(R, 20, false);                                                                         \
+    else if (form == 21) NRF_LAUNCH_MLP(R, 21, true);                                                                     \
+    else NRF_LAUNCH_MLP(R, 30, false);                                                                                    \
   } while (0)
   if (repeat > 1) NRF_LAUNCH_MLP_FORM(true); else NRF_LAUNCH_MLP_FORM(false);
 #undef NRF_LAUNCH_MLP_FORM
@@ -923,19 +927,18 @@ hipError_t launch_mlp_forward(const DevModel& M, const void* feat, const void* d
 
 hipError_t launch_network(const DevModel& M, const void* xyz, const void* dir, uint32_t n, void* sigma, void* rgb, hipStream_t st) {
   if (!n) return hipSuccess;
-  const uint64_t chunks = ((uint64_t)n + 63) / 64;
   if (M.stage == NET_GENERIC) {
     const int lds = gen_lds_bytes(M, 4);
     hipError_t e = allow_lds(network_kernel<NET_GENERIC>, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(network_kernel<NET_GENERIC>, dim3(grid_for(chunks, 4, 256 * 4)), dim3(256), lds, st, M,
+    hipLaunchKernelGGL(network_kernel<NET_GENERIC>, dim3(stage_grid(STAGE_NETWORK, n)), dim3(256), lds, st, M,
                        (const float*)xyz, (const float*)dir, n, (float*)sigma, (float*)rgb);
   } else if (M.stage == NET_WIDE) {
     const int lds = LDS_TOTAL_BYTES + (LDS_WFRAG_WIDE_BYTES - LDS_WFRAG_BYTES) + 4 * LDS_RAYD_BYTES;
-    hipLaunchKernelGGL(network_kernel<NET_WIDE>, dim3(grid_for(chunks, 4, 256 * 4)), dim3(256), lds, st, M,
+    hipLaunchKernelGGL(network_kernel<NET_WIDE>, dim3(stage_grid(STAGE_NETWORK, n)), dim3(256), lds, st, M,
                        (const float*)xyz, (const float*)dir, n, (float*)sigma, (float*)rgb);
   } else {
-    hipLaunchKernelGGL(network_kernel<NET_HOT>, dim3(grid_for(chunks, 4, 256 * 4)), dim3(256), LDS_TOTAL_BYTES, st, M,
+    hipLaunchKernelGGL(network_kernel<NET_HOT>, dim3(stage_grid(STAGE_NETWORK, n)), dim3(256), LDS_TOTAL_BYTES, st, M,
                        (const float*)xyz, (const float*)dir, n, (float*)sigma, (float*)rgb);
   }
   return hipGetLastError();
@@ -954,7 +957,7 @@ hipError_t launch_density_update(const void* sigma, uint32_t n, float decay, int
 
 hipError_t launch_generate_rays(const DevModel& M, const FrameParams& P, void* rays_o, void* rays_d, void* nears, void* fars,
                                 hipStream_t st) {
-  hipLaunchKernelGGL(generate_rays_kernel, dim3(grid_for((uint64_t)P.W * P.H)), dim3(256), 0, st, M, P, (float*)rays_o,
+  hipLaunchKernelGGL(generate_rays_kernel, dim3(stage_grid(STAGE_GENERATE_RAYS, (uint64_t)P.W * P.H)), dim3(256), 0, st, M, P, (float*)rays_o,
                      (float*)rays_d, (float*)nears, (float*)fars);
   return hipGetLastError();
 }
@@ -963,11 +966,11 @@ hipError_t launch_march(const DevModel& M, float dt_gamma, const void* rays_o, c
                         const void* fars, uint32_t n, uint32_t n_step, void* xyzs, void* dirs, void* deltas, hipStream_t st, uint32_t perturb) {
   if (!n) return hipSuccess;
   if (M.coarse_shift)
-    hipLaunchKernelGGL(march_kernel<true>, dim3(grid_for(n)), dim3(256), 0, st, M, dt_gamma, (const float*)rays_o,
+    hipLaunchKernelGGL(march_kernel<true>, dim3(stage_grid(STAGE_MARCH, n)), dim3(256), 0, st, M, dt_gamma, (const float*)rays_o,
                        (const float*)rays_d, (const float*)rays_t, (const float*)fars, n, n_step, (float*)xyzs, (float*)dirs,
                        (float*)deltas, perturb);
   else
-    hipLaunchKernelGGL(march_kernel<false>, dim3(grid_for(n)), dim3(256), 0, st, M, dt_gamma, (const float*)rays_o,
+    hipLaunchKernelGGL(march_kernel<false>, dim3(stage_grid(STAGE_MARCH, n)), dim3(256), 0, st, M, dt_gamma, (const float*)rays_o,
                        (const float*)rays_d, (const float*)rays_t, (const float*)fars, n, n_step, (float*)xyzs, (float*)dirs,
                        (float*)deltas, perturb);
   return hipGetLastError();
@@ -976,14 +979,14 @@ hipError_t launch_march(const DevModel& M, float dt_gamma, const void* rays_o, c
 hipError_t launch_composite(const void* sigmas, const void* rgbs, const void* deltas, uint32_t n, uint32_t n_step, void* rays_t,
                             void* state, hipStream_t st) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(composite_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const float*)sigmas, (const float*)rgbs,
+  hipLaunchKernelGGL(composite_kernel, dim3(stage_grid(STAGE_COMPOSITE, n)), dim3(256), 0, st, (const float*)sigmas, (const float*)rgbs,
                      (const float*)deltas, n, n_step, (float*)rays_t, (float*)state);
   return hipGetLastError();
 }
 
 hipError_t launch_untile(const void* gathered, int shard_count, int tiles_per_shard, int C, int W, int H, int n_views, void* out,
                          hipStream_t st) {
-  hipLaunchKernelGGL(untile_kernel, dim3(grid_for((uint64_t)W * H * n_views)), dim3(256), 0, st, (const float*)gathered, shard_count,
+  hipLaunchKernelGGL(untile_kernel, dim3(stage_grid(STAGE_UNTILE, (uint64_t)W * H * n_views)), dim3(256), 0, st, (const float*)gathered, shard_count,
                      tiles_per_shard, C, W, H, (W + 7) / 8, n_views, (float*)out);
   return hipGetLastError();
 }
@@ -1000,7 +1003,7 @@ __global__ __launch_bounds__(256) void quantize_rgbd8_kernel(const float4* __res
 
 hipError_t launch_quantize_rgbd8(const void* rgba, const void* depth, uint64_t n, void* out, hipStream_t st) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(quantize_rgbd8_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const float4*)rgba, (const float*)depth, (size_t)n,
+  hipLaunchKernelGGL(quantize_rgbd8_kernel, dim3(stage_grid(STAGE_QUANTIZE_RGBD8, n)), dim3(256), 0, st, (const float4*)rgba, (const float*)depth, (size_t)n,
                      (uint32_t*)out);
   return hipGetLastError();
 }
@@ -1049,13 +1052,13 @@ __global__ __launch_bounds__(256) void untile_rgbd8_u8_kernel(const uint32_t* __
 hipError_t launch_untile_rgbd8_u8(const void* gathered, int shard_count, int tiles_per_shard, int W, int H, int n_views, void* rgb8,
                                   void* depth8, hipStream_t st) {
   const uint64_t work = (uint64_t)W * H * n_views / ((W & 3) == 0 ? 4 : 1);
-  hipLaunchKernelGGL(untile_rgbd8_u8_kernel, dim3(grid_for(work)), dim3(256), 0, st, (const uint32_t*)gathered, shard_count,
+  hipLaunchKernelGGL(untile_rgbd8_u8_kernel, dim3(stage_grid(STAGE_UNTILE_U8, work)), dim3(256), 0, st, (const uint32_t*)gathered, shard_count,
                      tiles_per_shard, W, H, (W + 7) / 8, n_views, (unsigned char*)rgb8, (unsigned char*)depth8);
   return hipGetLastError();
 }
 
 hipError_t launch_quantize(const void* rgba, const void* depth, int n, void* rgb8, void* depth8, hipStream_t st) {
-  hipLaunchKernelGGL(quantize_kernel, dim3(grid_for((uint64_t)n)), dim3(256), 0, st, (const float4*)rgba, (const float*)depth, n,
+  hipLaunchKernelGGL(quantize_kernel, dim3(stage_grid(STAGE_QUANTIZE, (uint64_t)n)), dim3(256), 0, st, (const float4*)rgba, (const float*)depth, n,
                      (unsigned char*)rgb8, (unsigned char*)depth8);
   return hipGetLastError();
 }
