@@ -52,19 +52,13 @@ __global__ __launch_bounds__(256) void meshcc_hook_kernel(const uint32_t* __rest
     const uint32_t a = triangles[3 * (uint64_t)t], b = triangles[3 * (uint64_t)t + 1], c = triangles[3 * (uint64_t)t + 2];
     if (!meshcc_triangle_valid(a, b, c, n_vertices)) continue;
     const MeshccHook h = meshcc_hook(parent, a, b, c);
-    // (selects, not a loop over root[]: nothing private is indexed by a run-time value)
-    if (h.root[0] != h.low) lowered = (atomicMin(&parent[h.root[0]], h.low) > h.low) || lowered;
-    if (h.root[1] != h.low && h.root[1] != h.root[0]) lowered = (atomicMin(&parent[h.root[1]], h.low) > h.low) || lowered;
-    if (h.root[2] != h.low && h.root[2] != h.root[0] && h.root[2] != h.root[1]) lowered = (atomicMin(&parent[h.root[2]], h.low) > h.low) || lowered;
+    lowered = meshcc_hook_lower(h, [parent](uint32_t root, uint32_t low) { return atomicMin(&parent[root], low); }) || lowered;
   }
   if (lowered) *changed = 1u;
 }
 
 __global__ __launch_bounds__(256) void meshcc_compress_kernel(uint32_t* parent, uint32_t n_vertices) {
-  MESHCC_FOR(v, n_vertices) {
-    const uint32_t r = meshcc_root(parent, v);
-    if (r != parent[v]) parent[v] = r;
-  }
+  MESHCC_FOR(v, n_vertices) meshcc_compress(parent, v, [parent](uint32_t x, uint32_t r) { parent[x] = r; });
 }
 
 __global__ __launch_bounds__(256) void meshcc_roots_kernel(const uint32_t* __restrict__ labels, uint32_t n_vertices, uint32_t* __restrict__ codes) {

@@ -51,14 +51,37 @@ struct MeshccHook {
   uint32_t root[3];
   uint32_t low;
 };
-NRF_MESHCC_HD inline MeshccHook meshcc_hook(const uint32_t* parent, uint32_t a, uint32_t b, uint32_t c) {
+// (root(x): the walk from x.  host/meshcc_stale_check.cpp hands every walk loads of its own; to everyone else it is meshcc_root)
+template <class Root>
+NRF_MESHCC_HD inline MeshccHook meshcc_hook_of(Root&& root, uint32_t a, uint32_t b, uint32_t c) {
   MeshccHook h;
-  h.root[0] = meshcc_root(parent, a);
-  h.root[1] = meshcc_root(parent, b);
-  h.root[2] = meshcc_root(parent, c);
+  h.root[0] = root(a);
+  h.root[1] = root(b);
+  h.root[2] = root(c);
   const uint32_t ab = h.root[0] < h.root[1] ? h.root[0] : h.root[1];
   h.low = ab < h.root[2] ? ab : h.root[2];
   return h;
+}
+NRF_MESHCC_HD inline MeshccHook meshcc_hook(const uint32_t* parent, uint32_t a, uint32_t b, uint32_t c) {
+  return meshcc_hook_of([parent](uint32_t x) { return meshcc_root(parent, x); }, a, b, c);
+}
+// the stores of a hook: every root that is not the minimum gets lower(root, low), which makes parent[root] = min(parent[root], low) and
+// returns the value it found there (the kernel's is one device-scope atomicMin); true if any of them was above low.  Three selects,
+// not a loop over root[]: nothing private is indexed by a run-time value.  A root named twice is lowered once.
+template <class Lower>
+NRF_MESHCC_HD inline bool meshcc_hook_lower(const MeshccHook& h, Lower&& lower) {
+  bool lowered = false;
+  if (h.root[0] != h.low) lowered = (lower(h.root[0], h.low) > h.low) || lowered;
+  if (h.root[1] != h.low && h.root[1] != h.root[0]) lowered = (lower(h.root[1], h.low) > h.low) || lowered;
+  if (h.root[2] != h.low && h.root[2] != h.root[0] && h.root[2] != h.root[1]) lowered = (lower(h.root[2], h.low) > h.low) || lowered;
+  return lowered;
+}
+// compress of one vertex: store(v, root(v)) unless parent[v] holds it already.  parent is what the lane's loads return, store writes
+// the array itself (to the host they are one)
+template <class Store>
+NRF_MESHCC_HD inline void meshcc_compress(const uint32_t* parent, uint32_t v, Store&& store) {
+  const uint32_t r = meshcc_root(parent, v);
+  if (r != parent[v]) store(v, r);
 }
 // a triangle of a mesh of n_vertices vertices that names a vertex beyond them joins nothing (nrf_extract_mesh never makes one)
 NRF_MESHCC_HD inline bool meshcc_triangle_valid(uint32_t a, uint32_t b, uint32_t c, uint32_t n_vertices) {
@@ -122,13 +145,13 @@ inline MeshccParts meshcc_label_host(uint32_t n_vertices, const uint32_t* triang
       const uint32_t a = triangles[3 * t], b = triangles[3 * t + 1], c = triangles[3 * t + 2];
       if (!meshcc_triangle_valid(a, b, c, n_vertices)) continue;
       const MeshccHook h = meshcc_hook(parent.data(), a, b, c);
-      for (int k = 0; k < 3; ++k)
-        if (h.root[k] != h.low && h.low < parent[h.root[k]]) {
-          parent[h.root[k]] = h.low;
-          changed = true;
-        }
+      changed = meshcc_hook_lower(h, [&parent](uint32_t root, uint32_t low) {
+                  const uint32_t old = parent[root];
+                  if (low < old) parent[root] = low;
+                  return old;
+                }) || changed;
     }
-    for (uint32_t v = 0; v < n_vertices; ++v) parent[v] = meshcc_root(parent.data(), v);
+    for (uint32_t v = 0; v < n_vertices; ++v) meshcc_compress(parent.data(), v, [&parent](uint32_t x, uint32_t r) { parent[x] = r; });
     ++P.n_rounds;
   }
   P.rows.resize(n_vertices);

@@ -301,3 +301,98 @@ def test_the_check_program_is_the_replay_on_the_fields(check_program, name):
             print(f"{name}: {g[2]} rounds of hook + compress in the serial reference")
     assert kept[0] == len(t) and kept[-1] == 0 and kept[-2] == 0  # (min_triangles = 10^9 keeps nothing, with or without the flag)
     assert kept[1] == int(f.parts.table[:, 2].max())  # (0, KEEP_LARGEST)
+
+
+# ---------------------------------------------------------------- 3. the labelling under stale loads
+STALE_SEEDS = 64
+STALE_FIELDS = ["snake", "balls", "twins", "noise17", "dots"]
+
+
+@pytest.fixture(scope="module")
+def stale_program(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path_factory.mktemp("meshcc_stale") / "meshcc_stale_check"
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-o", str(exe), str(HOST / "meshcc_stale_check.cpp")], check=True)
+    return exe
+
+
+def _run_stale(exe, problems, seeds=STALE_SEEDS):
+    """{name: (labels, least rounds, most rounds, host rounds, walks, stale walks)} of the stale-load program on [(name, nv, triangles)]"""
+    text = "".join(f"{name} {nv} {len(np.asarray(t).reshape(-1)) // 3} {seeds}\n" + " ".join(map(str, np.asarray(t, np.int64).reshape(-1).tolist())) + "\n"
+                   for name, nv, t in problems)
+    out = subprocess.run([str(exe)], input=text, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert f"meshcc_stale_check: {len(problems)} problems" in out.stderr
+    lines, at, res = out.stdout.splitlines(), 0, {}
+    for name, nv, t in problems:
+        head = lines[at].split()
+        assert head[:4] == ["mesh", name, str(nv), str(len(np.asarray(t).reshape(-1)) // 3)] and head[4:6] == ["runs", str(2 * seeds)], head
+        assert [head[6], head[9], head[11], head[13]] == ["rounds", "host", "walks", "stale"], head
+        rows = lines[at + 1:at + 1 + nv]
+        assert len(rows) == nv and all(r.startswith("l ") for r in rows)
+        res[name] = (np.array([r[2:] for r in rows], np.int64).astype(np.uint32), int(head[7]), int(head[8]), int(head[10]), int(head[12]), int(head[14]))
+        at += 1 + nv
+    assert at == len(lines)
+    return res
+
+
+def _hand_made():
+    """[(name, nv, triangles)]: each list with ascending, descending and shuffled vertex numbering; an index >= nv stays invalid"""
+    lists = {
+        "fan": (10, [(0, i, i + 1) for i in range(1, 9)]),
+        "strip": (40, [(i, i + 1, i + 2) for i in range(38)]),
+        "pair": (5, [(0, 1, 2), (2, 3, 4)]),                                   # two triangles that share one vertex
+        "lonely": (6, [(0, 1, 2), (2, 4, 5)]),                                 # vertex 3 is named by no triangle
+        "invalid": (9, [(0, 1, 2), (2, 3, 9), (3, 4, 5), (5, 6, 0xffffffff), (6, 7, 8), (8, 4, 3)]),
+        "comb": (64, [(i, i + 1, 63 - i) for i in range(0, 31)] + [(2 * i, 2 * i + 1, 62) for i in range(31)]),
+    }
+    out = []
+    for name, (nv, tri) in lists.items():
+        t = np.array(tri, np.int64).reshape(-1, 3)
+        for order, perm in (("up", np.arange(nv)), ("down", np.arange(nv)[::-1]), ("mixed", np.random.default_rng(nv).permutation(nv))):
+            out.append((f"{name}_{order}", nv, np.where(t < nv, perm[np.minimum(t, nv - 1)], t)))
+    return out
+
+
+def test_the_stale_make_target():
+    mk = (HOST / "Makefile").read_text()
+    assert re.search(r"^meshcc_stale_asan: meshcc_stale_check$", mk, re.M)
+    rule = mk.split("meshcc_stale_check: meshcc_stale_check.cpp ../csrc/nrf_meshcc_plan.h")[1].split("\n# ")[0]
+    assert "-fsanitize=address,undefined" in rule and "-fno-sanitize-recover=all" in rule
+    assert "meshcc_stale_check" in mk.split("\nclean:")[1].split("\n#")[0]
+    # one text: the kernels, the serial reference and the stale-load program call the same hook and compress
+    plan = (ROOT / "nerf-cuda_amd" / "csrc" / "nrf_meshcc_plan.h").read_text()
+    kernels = (ROOT / "nerf-cuda_amd" / "csrc" / "nrf_kernels_meshcc.hip").read_text()
+    program = (HOST / "meshcc_stale_check.cpp").read_text()
+    for fn in ("meshcc_hook_lower(", "meshcc_compress("):
+        assert plan.count(fn) >= 2 and fn in kernels and fn in program, fn
+    assert "atomicMin(&parent[root], low)" in kernels
+    assert "meshcc_hook_of(" in program and "meshcc_root(" in program and "meshcc_triangle_valid(" in program
+
+
+def test_stale_loads_on_hand_made_lists(stale_program):
+    problems = _hand_made()
+    assert len(problems) == 18
+    got = _run_stale(stale_program, problems)
+    for name, nv, t in problems:
+        lab, lo, hi, host, walks, stale = got[name]
+        want = cr.parts(nv, t[np.all(t < nv, axis=1)])  # (the replay knows no invalid index: such a triangle joins nothing)
+        assert np.array_equal(lab, want.labels), name
+        assert 1 <= lo <= hi <= nv + 1, (name, lo, hi)
+        assert stale > 0 or nv < 10, name  # the memory did hand out old values (two triangles may leave none to hand out)
+        print(f"{name}: {nv} vertices, rounds {lo} .. {hi} over {2 * STALE_SEEDS} runs (serial {host}), {stale} of {walks} walks loaded an old value")
+    assert got["lonely_up"][0].tolist() == [0, 0, 0, 3, 0, 0] and got["invalid_up"][0].tolist() == [0, 0, 0, 3, 3, 3, 3, 3, 3]
+
+
+@pytest.mark.parametrize("name", STALE_FIELDS)
+def test_stale_loads_on_the_fields(stale_program, name):
+    f = field(name)
+    nv = len(f.mesh.vertices)
+    lab, lo, hi, host, walks, stale = _run_stale(stale_program, [(name, nv, f.mesh.triangles)])[name]
+    assert np.array_equal(lab, f.parts.labels)
+    assert 2 <= lo <= hi <= nv + 1
+    assert stale > 0
+    print(f"{name}: {nv} vertices, rounds {lo} .. {hi} over {2 * STALE_SEEDS} runs (serial {host}), {stale} of {walks} walks loaded an old value")

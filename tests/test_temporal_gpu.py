@@ -198,6 +198,50 @@ def test_the_motion_vectors_are_the_replays():
     ctx.close()
 
 
+def test_the_motion_vectors_past_one_grid_stride_pass():
+    """motion_kernel's launch is capped at 2048 x 256 lanes: 1023 x 513 = 524 799 render pixels take a second, ragged trip (511 pixels,
+    no multiple of 256).  Bit for bit against the replay; the odd alphas and depths of the test above sit in the first trip and again
+    beyond pixel 524 288; 64 rows after the plane stay as they were."""
+    import torch
+    import synthetic as syn
+    desc, keep, cfg = _model()
+    W, H, OW, OH, GUARD = 1023, 513, 1300, 700, 64
+    assert W * H > 2048 * 256 and (W * H) % 256 != 0
+    ctx = nh.NerfHip(0)
+    ctx.load_model(desc)
+    ctx.set_resolution(W, H)
+    cam, pose = np.asarray(syn.default_camera(W, H), np.float32), np.asarray(syn.orbit_pose(20.0, 30), np.float32)
+    prev_cam, prev_pose = cam + F([0.5, -0.5, 0.3, 0.2]), np.asarray(syn.orbit_pose(23.0, 31), np.float32)
+    o, d = torch.empty((H, W, 3), device="cuda"), torch.empty((H, W, 3), device="cuda")
+    ctx.generate_rays(cam - F([0, 0, 0.25, -0.125]), pose, o.data_ptr(), d.data_ptr(), None, None)
+    rng = np.random.default_rng(40)
+    rgba = rng.uniform(0.0, 1.0, (H, W, 4)).astype(np.float32)
+    depth = (rgba[..., 3] * rng.uniform(0.2, 2.0, (H, W))).astype(np.float32)
+    for row, col in ((0, 0), (H - 1, 600)):
+        assert row * W + col + 10 <= 2048 * 256 if row == 0 else row * W + col > 2048 * 256
+        rgba[row, col:col + 4, 3] = F([0.0, np.nan, 0.25, 1.0])
+        depth[row, col + 4:col + 8] = F([np.inf, np.nan, -1.0, 0.0])
+        rgba[row, col + 8:col + 10, 3] = F([0.5, np.nextafter(F(0.5), F(0))])  # the two sides of min_alpha
+    sentinel = F(-77.25)
+    out = torch.full((H + GUARD, W, 2), float(sentinel), device="cuda")
+    dev_rgba, dev_depth = _device(rgba), _device(depth)
+    torch.cuda.synchronize()
+    ctx.motion_vectors(o.data_ptr(), d.data_ptr(), dev_rgba.data_ptr(), dev_depth.data_ptr(), W, H, OW, OH, cam, pose, prev_cam, prev_pose,
+                       out.data_ptr(), min_alpha=0.5)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    want = tr.motion_vectors(o.cpu().numpy(), d.cpu().numpy(), rgba[..., 3], depth, OW, OH, 0.5, tr.camera(pose, desc.scale, cam),
+                             tr.camera(prev_pose, desc.scale, prev_cam))
+    assert want.shape == (H, W, 2)
+    bad = np.nonzero(ur.bits(got[:H]) != ur.bits(want))
+    assert len(bad[0]) == 0, (len(bad[0]), [b[:5] for b in bad])
+    assert np.all(ur.bits(got[H:]) == ur.bits(np.full(1, sentinel, np.float32))[0])
+    assert not np.any(ur.bits(want) == ur.bits(np.full(1, sentinel, np.float32))[0])  # every pixel of the plane was written
+    second = want.reshape(-1, 2)[2048 * 256:]
+    assert len(second) == 511 and np.isfinite(second).all() and np.abs(second).max() > 0.5
+    ctx.close()
+
+
 def test_eight_jittered_frames_of_a_model_come_closer_to_the_full_resolution_render():
     """Render 48 x 32 with 8 jittered cameras, present, accumulate to 96 x 64: closer (PSNR) to a direct 96 x 64 render of the same view than
     nrf_rb_upscale of the unjittered frame is.  A relative condition; both values are printed."""
